@@ -1,6 +1,6 @@
 """bench.py — denoising-step throughput of the HIP path on synthetic 23-atom R/TS/P triples.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1, either form (one process per GPU, backend nccl = RCCL):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...      (no WORLD_SIZE in the environment: bench.py starts that launcher itself as a CHILD
@@ -9,6 +9,11 @@
 A "step" is one EGNNDynamics.forward call (= one denoising step of the T=1000 sampler) on a batch of
 64 reactions per GPU (BASELINE.json configs[1]); reactions are independent, so ranks run replicas with
 no data-path collective (weak scaling).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the benchmark measures (roofline /
+per-family kernel times, the T = 1000 sampling run, the training leg, the split-precision line, config 5, the general-edge-list path, the
+CPU baseline), all outside the headline's timed region.  --dump-outputs DIR writes what the timed path computed in its last timed step
+as DIR/<name>.npy (inputs are seeded: the same arguments give the same inputs in every run).
 """
 import argparse
 import json
@@ -149,6 +154,28 @@ def pmc_traffic(kernel: str, prefix: str = None, tag: str = None):
         f"HBM bytes per step over all launches of this kernel: 2 x FETCH_SIZE + WRITE_SIZE, profiles/{prefix}_pmc_*.txt (same sources: stamp {source_stamp()})"
 
 
+DUMP_BYTES = 64 << 20
+
+
+def write_outputs(dirname: str, arrays) -> None:
+    """--dump-outputs: DIR/<name>.npy per array, float64 stays float64, everything else float32.  An array that would take the total
+    past 64 MB is replaced by a fixed sample of its flattened elements (seeded, sorted indices; DIR/<name>_sample_index.npy)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+        a = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+        if total + a.nbytes > DUMP_BYTES:
+            keep = max(1, min(a.size, (DUMP_BYTES - total) // (a.itemsize + 8)))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(dirname, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            total += idx.size * 8
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        total += a.nbytes
+
+
 def make_training_batch(B: int, n_atoms: int, seed: int, dev):
     """Synthetic Transition1x-shaped batch in the layout of dataset/base_dataset.py:55-88:
     per object {size [B], pos [n,3], one_hot [n,5] int64, charge [n,1] int64, mask [n]} + conditions [B,1], built on the host like a
@@ -183,8 +210,10 @@ def fwd_flops(E, A, A_act=None):
             "equi_edge": 2.0 * L * MAC_EQUI_EDGE * (A if A_act is None or A_act < 0 else A_act)}
 
 
-def train_leg(dyn, B, nf, dev, dist, world, steps, warmup, timing=True):
-    """One training step = DDPMTrainer.training_step (loss, HIP backward, one all-reduce, adaptive clip, AdamW)."""
+def train_leg(dyn, B, nf, dev, dist, world, steps, warmup, timing=True, family_pass=True, dump_dir=None):
+    """One training step = DDPMTrainer.training_step (loss, HIP backward, one all-reduce, adaptive clip, AdamW).
+    family_pass=False: no per-family kernel timing after the timed steps (a plain `--mode train` run); dump_dir: write what the last
+    timed step handed back (loss, gradient norm, the updated parameters) before anything else runs."""
     from oareactdiff_amd import _capi
     from oareactdiff_amd.trainer import DDPMTrainer
     # host_sync=False: the clip / skip decision and AdamW's scalars are taken on the device (oard_adamw_step_dev), so the timed steps
@@ -212,6 +241,11 @@ def train_leg(dyn, B, nf, dev, dist, world, steps, warmup, timing=True):
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if dump_dir is not None:
+        write_outputs(dump_dir, {"loss": torch.tensor([info["loss"]], dtype=torch.float64),
+                                 "grad_norm": torch.tensor([float("nan") if info.get("grad_norm") is None else info["grad_norm"]],
+                                                           dtype=torch.float64),
+                                 "parameters": torch.cat([p.detach().reshape(-1) for p in tr.params])})
     coll = tr.collective_report() if tr.collectives else None
     tr.time_collectives = False
     out = {"ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup, "batch_per_gpu": B, "loss": info["loss"],
@@ -221,6 +255,8 @@ def train_leg(dyn, B, nf, dev, dist, world, steps, warmup, timing=True):
     # two more steps with per-family kernel timing on rank 0; EVERY rank runs them (each step holds a collective).  The timed
     # steps above run the reverse sweep on two streams (weight-gradient work beside the cotangent chain), where per-launch
     # event times overlap and do not add up; the family pass runs the sweep on ONE stream (debug option train_dual = 0).
+    if not family_pass:
+        return out, dt
     L_ = _capi.lib()
     if timing:
         L_.oard_debug_option(b"train_dual", 0)
@@ -281,8 +317,9 @@ class Workload:
         self.ts = [torch.full((B, 1), (1000 - s) / 1000, device=dev) for s in range(8)]
 
     def step(self, dyn, i):
+        """One denoising call; returns its outputs (one [n_k, 3 + nf_k] tensor per object)."""
         with torch.no_grad():
-            dyn(self.inputs[i % len(self.inputs)], self.ei, self.ts[i % len(self.ts)], self.cond, self.nfs, self.cm)
+            return dyn(self.inputs[i % len(self.inputs)], self.ei, self.ts[i % len(self.ts)], self.cond, self.nfs, self.cm)[0]
 
 
 def input_seed(rank: int) -> int:
@@ -619,15 +656,21 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="reactions per GPU")
     ap.add_argument("--atoms", type=int, default=23, help="atoms per object")
     ap.add_argument("--pos-scale", type=float, default=1.0, help="scale of the N(0,1) positions (3: the 10 A cutoff bites; BASELINE configs[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--mode", choices=("sample", "train"), default="sample",
                     help="sample: one denoising call per step (BASELINE configs 2/3); train: one training step (config 4)")
-    ap.add_argument("--quick", action="store_true", help="skip the full T=1000 sampling run and the training leg")
+    ap.add_argument("--quick", action="store_true", help="with --full: skip the full T=1000 sampling run and the training leg")
     ap.add_argument("--precision", choices=("f32", "bf16x3"), default="f32",
                     help="bf16x3: the SECOND line - the two edge stages on the split-precision kernels (three bf16 terms per fp32 value, six "
                          "bf16 MFMAs per K block, fp32 accumulation: fp32-grade results, csrc/oard_edge_b3.h); inference only; the "
                          "fp32 kernels stay the default and the headline")
     ap.add_argument("--no-graph", action="store_true", help="launch-bound batches (B <= 8): eager launches instead of hipGraph replay")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: roofline / per-family kernel times (in --mode train: the family "
+                         "pass), the T=1000 sampling run, the training leg, the split-precision line, config 5, the general-edge-list "
+                         "path and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -660,6 +703,8 @@ def main():
         return dry_run(args, rank, world, dist, backend)
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
+    torch.manual_seed(input_seed(rank))                      # the training step's t and noise: same arguments, same inputs
+    dump_dir = args.dump_outputs if rank == 0 else None
 
     from oareactdiff_amd import _capi  # noqa: F401  (loads the library: fails loudly if it is missing)
 
@@ -668,7 +713,8 @@ def main():
     wl = Workload(B, nf, dev, input_seed(rank), pos_scale=args.pos_scale)
 
     if args.mode == "train":
-        leg, dt = train_leg(dyn, B, nf, dev, dist, world, args.steps, args.warmup, timing=(rank == 0))       # collective inside: all ranks
+        leg, dt = train_leg(dyn, B, nf, dev, dist, world, args.steps, args.warmup, timing=(rank == 0),       # collective inside: all ranks
+                            family_pass=args.full, dump_dir=dump_dir)
         dt_local = dt
         if dist is not None:
             tt = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
@@ -701,12 +747,12 @@ def main():
         return
 
     def eager_step(i):
-        wl.step(dyn, i)
+        return wl.step(dyn, i)
 
     # Launch-bound batches (B <= 8: ~100 launches of a few microseconds each per call): the same call captured once per
     # input set as a hipGraph and replayed - same kernels, same arithmetic (tests: bit-identical), no host launch cost.
     use_graph = B <= 8 and not args.no_graph
-    graphs = []
+    graphs, graph_outs = [], []
     if use_graph:
         eager_step(0)                                          # topology, packed weights, workspace, LDS attributes
         side = torch.cuda.Stream(device=dev)
@@ -717,14 +763,16 @@ def main():
         for k in range(len(wl.inputs)):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=side):
-                eager_step(k)
+                graph_outs.append(eager_step(k))                # the replay writes its outputs into these tensors
             graphs.append(g)
+    last = {}
 
     def step(i):
         if graphs:
             graphs[i % len(graphs)].replay()
+            last["out"] = graph_outs[i % len(graphs)]
         else:
-            eager_step(i)
+            last["out"] = eager_step(i)
 
     dt = timed_steps(step, args.steps, args.warmup, dev, dist)      # W warm-up steps, barrier + sync, K steps, sync + barrier
     dt_local = dt
@@ -735,26 +783,29 @@ def main():
     ranks = ranks_report(dist, rank, world, dev, dt_local, args.steps, None, timed_steps.busy)
     if not os.environ.get("OARD_BENCH_ALLOW_NAN"):          # (kernel ablation experiments produce garbage on purpose)
         assert int(dyn.last_status[0].item()) == 0, "NaN in the timed region"
+    if dump_dir is not None:                                 # the velocity / feature outputs of the last timed step, one array per object
+        write_outputs(dump_dir, {f"output_{name}": o for name, o in zip(dyn.fragment_names, last["out"])})
 
     # ---- everything below is outside the timed region, on rank 0 -------------------------------------------------------------------
     E, A = edge_counts(B, nf)
     roof = None
     skip = set(filter(None, os.environ.get("OARD_BENCH_SKIP", "").split(",")))     # debugging: legs to leave out
     std = (B, nf) == (64, 23)
-    if rank == 0 and "roofline" not in skip:               # per-kernel durations (HIP events on the launch stream)
+    if rank == 0 and args.full and "roofline" not in skip:      # per-kernel durations (HIP events on the launch stream)
         prefix = (PROFILE_TAG if args.precision == "f32" else PROFILE_TAG + "_bf16x3") if std else "no-PMC-pass-for-this-shape"
         roof = roofline_of(kernel_families(dyn, eager_step, dev), E, A, args.precision, prefix, dyn.active_inner_edges())
 
     # the real sampling loop (row N1): the BASELINE metric's reactions/s, MEASURED (T = 1000 unless --quick)
     sampler_leg = train = second = cfg5 = general = None
-    extra = rank == 0 and world == 1 and not os.environ.get("OARD_BENCH_ALLOW_NAN")     # N > 1: the other ranks wait in a barrier meanwhile
+    extra = args.full and rank == 0 and world == 1 and not os.environ.get("OARD_BENCH_ALLOW_NAN")   # N > 1: the other ranks wait in a barrier
     if extra and "sampler" not in skip:
         sampler_leg = sampler_run(dyn, wl, 12 if args.quick else 1000, dev)
     full = extra and not args.quick and args.precision == "f32"
     if full:
         # the remaining legs get what their stand-alone modes have: fresh modules and an allocator that starts empty (the training
         # step walks ~25 GB of tape / scratch; carved out of the other legs' left-overs it ran 5-8 % slower: 83 vs 77 ms measured)
-        graphs = wl = None
+        graphs = graph_outs = wl = None
+        last.clear()
         del dyn
         torch.cuda.empty_cache()
         if "train" not in skip:
@@ -793,7 +844,7 @@ def main():
             "config5": cfg5,
             "general_edge_lists": general,
         }
-        if not args.no_cpu_baseline and world == 1:          # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # reported on rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(nf)
         print(json.dumps(out))
     if dist is not None:

@@ -38,7 +38,7 @@ def test_profile_stamp_belongs_to_the_sources_in_the_tree():
 
 
 def test_committed_bench_line_carries_every_leg():
-    """The default `bench.py` run measures more than the headline: the T = 1000 loop, the training step, the split-precision line, config 5 and
+    """`bench.py --full` measures more than the headline: the T = 1000 loop, the training step, the split-precision line, config 5 and
     (round 6) the general-edge-list path beside the production kernels.  The committed line of the round has them all, and the two independent
     implementations of the network agree on the headline batch."""
     import bench

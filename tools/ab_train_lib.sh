@@ -3,7 +3,7 @@
 for s in "$@"; do
   export OARD_LIB=$GRAFT_REPO_ROOT/oareactdiff_amd/csrc/liboard_$s.so
   for i in 1 2; do
-    OARD_TRAIN_DUAL=0 python bench.py --mode train --steps 8 --warmup 2 2>/dev/null | tail -1 | python -c "
+    OARD_TRAIN_DUAL=0 python bench.py --full --mode train --steps 8 --warmup 2 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); t=d['train_step']
 print('lib $s', 'ms/step', round(d['ms_per_step'],2), t['families_ms_per_step'], 'loss', round(t['loss'],4))"

@@ -10,7 +10,7 @@ export OARD_PARTS=1
 # only fixed-distribution steps under the profiler: the (quick) sampling leg runs a diverging trajectory whose inner edges leave the cutoff -
 # EquiMessage then skips them, and its calls would pull the per-kernel averages of the trace down (round 5)
 export OARD_BENCH_SKIP=sampler
-B="python bench.py --steps 4 --warmup 2 --no-cpu-baseline --quick"
+B="python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --quick"
 python -c "import bench; print(bench.source_stamp())" > gpurun_out/${tag}_source_stamp.txt
 P=1    # sub-batches in this profiling configuration
 timeout 600 rocprofv3 --kernel-trace --stats -d gpurun_out/${tag}_trace -o t -- $B > gpurun_out/${tag}_trace.log 2>&1

@@ -10,7 +10,7 @@ export OARD_PARTS=1
 export OARD_BENCH_SKIP=sampler
 for v in n x3; do
   scale=1; [ $v = x3 ] && scale=3
-  B="python bench.py --batch 4 --atoms 128 --pos-scale $scale --steps 4 --warmup 2 --no-cpu-baseline --quick"
+  B="python bench.py --full --batch 4 --atoms 128 --pos-scale $scale --steps 4 --warmup 2 --no-cpu-baseline --quick"
   p=gpurun_out/${tag}_cfg5${v}
   timeout 300 rocprofv3 --kernel-trace --stats -d ${p}_trace -o t -- $B > ${p}_trace.log 2>&1
   python tools/prof_summary.py ${p}_trace/t_results.db > ${p}_kernel_trace_summary.txt

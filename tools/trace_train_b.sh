@@ -3,7 +3,7 @@
 B=$1; tag=$2
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for dual in 1 0; do
-  OARD_TRAIN_DUAL=$dual python bench.py --mode train --batch $B --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
+  OARD_TRAIN_DUAL=$dual python bench.py --full --mode train --batch $B --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); t=d['train_step']
 print('B $B dual $dual ms/step', round(d['ms_per_step'],2), t['families_ms_per_step'], 'kernels', t['hip_kernel_ms_per_step'])"
