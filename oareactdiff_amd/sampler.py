@@ -2,8 +2,9 @@
 
 `DiffusionSampler.sample` mirrors `EnVariationalDiffusion.sample`
 (oa_reactdiff/diffusion/en_diffusion.py:459-560): same arguments, same return value
-`(out_samples, fragments_masks)`.  Per step it issues one `oard_forward` and one `oard_sampler_step`
-(mu, CoM-free noise, CoM projection, pos_only feature reset fused); the schedule scalars come from a host
+`(out_samples, fragments_masks)`.  Per step it issues one `oard_forward` and the step kernel `oard_sampler_step`
+(mu, CoM-free noise, CoM projection, pos_only feature reset fused; launched a second time as a bare projection after the steps
+that project, `_project_again`); the schedule scalars come from a host
 table, the NaN flag stays on the device, and the reference's four `.item()` asserts per step are gone, so
 the loop never synchronises the host with the GPU."""
 from __future__ import annotations
@@ -33,6 +34,8 @@ class DiffusionSampler:
         alpha_t^2 s^2 + sigma_t^2 (= 1 for s = 1, the distribution of the headline's inputs) and every network call sees a
         molecule-sized cloud, as a trained model's would.  One in-place axpy per object and step on the loop's stream; the network
         call itself is untouched.  Used by bench.py's T = 1000 line and tests/test_configs.py (the float64 replay adds the same term).
+        The term applies after EVERY network call of `sample` and of `inpaint` (the denoising calls at time (s + 1) / T and the final call
+        at time 0; in `inpaint` the objects of `frag_fixed` receive it too, and their denoised branch is discarded as before).
 
         `on_nan`: what to do when any network call of a run predicted a NaN displacement.  The reference replaces that
         step's velocity by randn, prints a warning and keeps sampling (egnn_dynamics.py:138-143) - one host sync per
@@ -108,9 +111,29 @@ class DiffusionSampler:
         cfg = self.dynamics._config()
         n = len(self.node_nfs)
         arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts]) if ts is not None else None
+        first = [torch.empty_like(o) for o in out] if mode in (0, 4) else out
         rc = L.oard_sampler_step(C.byref(cfg), topo.handle, mode, arr(z), arr(eh), arr(noise), arr(h0),
-                                 C.c_float(a), C.c_float(b), C.c_float(c), 1 if self.pos_only else 0, arr(out), stream)
+                                 C.c_float(a), C.c_float(b), C.c_float(c), 1 if self.pos_only else 0, arr(first), stream)
         _capi.check(rc, "oard_sampler_step")
+        if first is not out:
+            self._project_again(topo, first, h0, out, stream)
+
+    def _project_again(self, topo, x, h0, out, stream):
+        """Second CoM projection of a mode 0 / mode 4 result: out = x - mean_group(x) on the positions, everything else copied (the
+        step kernel in mode 4 with a = 1, c = 0; `x` itself stands in for the noise operand, which c = 0 switches off, so nothing
+        else is read and a finite x gives a finite out).  The kernel adds a group's rows up in a float32 running sum, so the mean it
+        removes carries ~1e-7 of the UN-projected values per row: when those share an offset far above their spread (|mean| ~ 60,
+        spread ~ 1) a mean of 3e-6 ... 1e-5 max|out| stays in the output.  The second pass sums values of the size of the output
+        and leaves 1e-8.  The loops' own operands are CoM-free, so for them the pass changes last bits only; it is here because the
+        wrappers promise a CoM-free result for ANY operands.  (The one-launch form - float64 group sums inside k_sampler_step -
+        belongs to a change that re-collects the profile passes, which are tied to the kernel sources: tests/test_docs_in_step.py.)"""
+        L = _capi.lib()
+        cfg = self.dynamics._config()
+        n = len(self.node_nfs)
+        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts]) if ts is not None else None
+        rc = L.oard_sampler_step(C.byref(cfg), topo.handle, 4, arr(x), None, arr(x), arr(h0),
+                                 C.c_float(1.0), C.c_float(0.0), C.c_float(0.0), 1 if self.pos_only else 0, arr(out), stream)
+        _capi.check(rc, "oard_sampler_step (second projection)")
 
     def _step_kernel_dev(self, topo, mode, z, eh, noise, h0, coef, out, stream):
         """As `_step_kernel` with the schedule scalars in device memory (`coef` [3]): the launch a hipGraph replays."""
@@ -118,16 +141,20 @@ class DiffusionSampler:
         cfg = self.dynamics._config()
         n = len(self.node_nfs)
         arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts]) if ts is not None else None
+        first = [torch.empty_like(o) for o in out] if mode in (0, 4) else out
         rc = L.oard_sampler_step_dev(C.byref(cfg), topo.handle, mode, arr(z), arr(eh), arr(noise), arr(h0), coef.data_ptr(),
-                                     1 if self.pos_only else 0, arr(out), stream)
+                                     1 if self.pos_only else 0, arr(first), stream)
         _capi.check(rc, "oard_sampler_step_dev")
+        if first is not out:
+            self._project_again(topo, first, h0, out, stream)
 
-    def _graphed_steps(self, dyn, topo, timesteps, za, draw, h0d, edge_index, conditions, n_frag_switch, combined_mask, dev):
+    def _graphed_steps(self, dyn, topo, timesteps, za, draw, h0d, edge_index, conditions, n_frag_switch, combined_mask, dev,
+                       step_callback=None):
         """The T ancestral steps of `sample` as ONE captured hipGraph replayed T times (small batches are launch-bound:
         ~100 kernel launches per step).  The per-step scalars live in device tables indexed by a device-side step counter:
         t, the three schedule coefficients and the step's noise draw; the graph holds [table lookups, oard_forward,
-        oard_sampler_step_dev, z <- z_new, counter += 1].  Same kernels and same arithmetic as the eager loop, so the
-        result is bit-identical.  Captured on a side stream after an eager warm-up step, as torch.cuda.graph requires."""
+        oard_sampler_step_dev, its second projection (oard_sampler_step with constant scalars), z <- z_new, counter += 1].  Same
+        kernels and same arithmetic as the eager loop, so the result is bit-identical.  Captured on a side stream after an eager warm-up step, as torch.cuda.graph requires."""
         n_obj = len(self.node_nfs)
         steps = list(reversed(range(timesteps)))
         coefs = [self.schedule.step(s, timesteps) for s in steps]
@@ -176,6 +203,8 @@ class DiffusionSampler:
             refill(min(block, timesteps))
             one_step()
             done, in_block = 1, 1
+            if step_callback is not None:
+                step_callback(done)
             if timesteps > 1:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=side):
@@ -187,6 +216,8 @@ class DiffusionSampler:
                     g.replay()
                     done += 1
                     in_block += 1
+                    if step_callback is not None:
+                        step_callback(done)
         torch.cuda.current_stream(dev).wait_stream(side)
         return z
 
@@ -200,8 +231,9 @@ class DiffusionSampler:
         `graph`: replay the step as a captured hipGraph (`_graphed_steps`; bit-identical to the eager loop, noise drawn in
         blocks of at most `self.noise_block_bytes`); None = automatically for launch-bound batches (n_samples <= 8, one returned
         frame) unless the caller's stream is itself being captured (then the eager loop runs, which is capturable).
-        `step_callback(i)`: called on the host after the i-th network call of the eager loop has been enqueued (i = 1 ... T; progress
-        bars, timing events - it must not synchronise if the loop is to stay free of host waits)."""
+        `step_callback(i)`: called on the host after the i-th network call has been enqueued (i = 1 ... T; progress bars, timing
+        events - it must not synchronise if the loop is to stay free of host waits).  The graphed loop calls it after the warm-up step
+        and after every replay, with its capture stream current."""
         timesteps = self.T if timesteps is None else timesteps
         assert 0 < return_frames <= timesteps and timesteps % return_frames == 0       # en_diffusion.py:473-475
         assert h0 is not None if self.pos_only else True
@@ -245,7 +277,7 @@ class DiffusionSampler:
                 if use_graph:
                     assert return_frames == 1, "intermediate frames need the eager loop"
                     za = self._graphed_steps(dyn, topo, timesteps, za, draw, h0d, edge_index, conditions, n_frag_switch,
-                                             combined_mask, dev)
+                                             combined_mask, dev, step_callback)
                     call = timesteps + 1
                 for s in (reversed(range(timesteps)) if not use_graph else ()):
                     co = self.schedule.step(s, timesteps)
@@ -371,6 +403,7 @@ class DiffusionSampler:
                 zt = new()
                 self._step_kernel(topo, 2, None, None, draw(), hsel, 0.0, 0.0, 1.0, zt, stream)
                 t_table = torch.arange(timesteps + 1, device=dev, dtype=torch.float32) / timesteps
+                ptab = self._prior_table(timesteps, dev) if self.prior_std is not None else None
                 schedule = get_repaint_schedule(resamplings, jump_length, timesteps)
                 s = timesteps - 1
                 for i, n_denoise in enumerate(schedule):
@@ -380,6 +413,8 @@ class DiffusionSampler:
                         self._step_kernel(topo, 3, xf, None, draw(), hsel, a_s, 0.0, sig_s, known, stream)   # :797-805
                         co = self.schedule.step(s, timesteps)
                         eps_hat, _ = dyn(zt, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
+                        if ptab is not None:
+                            self._add_prior(eps_hat, zt, ptab[s + 1: s + 2])
                         unknown = new()
                         self._step_kernel(topo, 0, zt, eps_hat, draw(), hsel, co.alpha_ts, co.c_eps, co.sigma, unknown, stream)
                         zt = [known[k] if k in frag_fixed else unknown[k] for k in range(n_obj)]            # :827-830
@@ -393,6 +428,8 @@ class DiffusionSampler:
                         s -= 1
                 fc = self.schedule.final()
                 eps_hat, _ = dyn(zt, edge_index, t_table[0:1], conditions, n_frag_switch, combined_mask)
+                if ptab is not None:
+                    self._add_prior(eps_hat, zt, ptab[0:1])
                 x = new()
                 self._step_kernel(topo, 1, zt, eps_hat, draw(), None, fc.inv_alpha_0, fc.sigma_0, fc.sigma_x, x, stream)
                 self.last_x = x
