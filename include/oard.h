@@ -398,6 +398,8 @@ int oard_nan_replace(const oard_config* cfg, const oard_topology* topo, const in
  *                    raw N(0,1) position noise, z_t = alpha_t x + sigma_t eps with gamma = gamma_table[t_int[b]].
  * oard_loss_terms    the rest of it + DDPMModule.compute_loss (pl_trainer.py:208-282, l2 training form): per-sample nll [B], logged
  *                    terms [2 n_obj][B] (normalised and un-normalised error per object) and d(mean_b nll)/d(network output).
+ *                    An empty (sample, object) group contributes 0 to nll and gets exact zeros in its two `terms` entries (the
+ *                    reference divides by the group's size there and yields NaN).
  * oard_adamw_step    torch.optim.AdamW(amsgrad) (pl_trainer.py:150) over one flat bucket, gradient-clipping factor folded in.
  * norm_values / norm_biases [3], scales [n_obj]: host arrays.  t_int [B] float32 (device), gamma table [T+1] (device). */
 int oard_loss_prepare(const oard_config* cfg, const oard_topology* topo, const float* const* pos_dev, const int64_t* const* one_hot_dev,

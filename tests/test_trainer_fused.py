@@ -20,6 +20,27 @@ def _trainer(c, dev, fused, pos_only, **kw):
                        fused=fused, **kw)
 
 
+def _fused_against_autograd(make, reps, cond, t_int, draws, label):
+    """Generic (DiffusionLoss + autograd into the bucket) against fused on the same batch, time steps and draws; `make(fused)` builds
+    the trainer."""
+    tg = make(False)
+    tg._bucket.zero_()
+    nll_g, info_g = tg.compute_loss((reps(), cond), training=True, t_int=t_int, draw=draws())
+    nll_g.mean(0).backward()
+    tf = make(True)
+    tf._bucket.zero_()
+    nll_f, terms = tf._fused_forward_backward((reps(), cond), t_int=t_int, draw=draws())
+    e_nll = float(((nll_f - nll_g.detach()).abs() / nll_g.detach().abs().clamp(min=1e-6)).max())
+    gd = float((tf.flat_grad - tg.flat_grad).norm() / tg.flat_grad.norm())
+    gmax = float((tf.flat_grad - tg.flat_grad).abs().max() / tg.flat_grad.abs().max())
+    print(f"{label}: nll rel {e_nll:.2e}; gradient bucket |d|_2/|g|_2 {gd:.2e}, max|d|/max|g| {gmax:.2e}")
+    assert e_nll <= 2e-6 and gd <= 2e-6 and gmax <= 2e-6
+    K = 3
+    for k in range(K):
+        assert abs(float(terms[k].mean()) / (tf.loss.scales[k] + 1e-4) - info_g[f"error_t_{k}"]) <= 2e-6 * max(1.0, abs(info_g[f"error_t_{k}"]))
+        assert abs(float(terms[K + k].mean()) - info_g[f"unorm_error_t_{k}"]) <= 2e-6 * max(1.0, abs(info_g[f"unorm_error_t_{k}"]))
+
+
 @pytest.mark.parametrize("name,pos_only", [("g9_grad_prod_l2", False), ("g9_grad_h32", True), ("g9_grad_prod_n23", True)])
 def test_fused_loss_and_gradients_equal_the_autograd_formulation(name, pos_only):
     c = GradCase(name)                      # g9_grad_prod_l2 holds a t_int = 0 sample: the discretised-likelihood terms are live
@@ -31,24 +52,41 @@ def test_fused_loss_and_gradients_equal_the_autograd_formulation(name, pos_only)
     def draws():
         it = iter(range(c.meta["n_randn"]))
         return lambda shape: torch.from_numpy(c.z[f"randn{next(it)}"]).to(dev)
-    # generic: DiffusionLoss + autograd into the bucket
-    tg = _trainer(c, dev, False, pos_only)
-    tg._bucket.zero_()
-    nll_g, info_g = tg.compute_loss((c.reps(torch.float32, dev), cond), training=True, t_int=t_int, draw=draws())
-    nll_g.mean(0).backward()
-    # fused
-    tf = _trainer(c, dev, True, pos_only)
-    tf._bucket.zero_()
-    nll_f, terms = tf._fused_forward_backward((c.reps(torch.float32, dev), cond), t_int=t_int, draw=draws())
-    e_nll = float(((nll_f - nll_g.detach()).abs() / nll_g.detach().abs().clamp(min=1e-6)).max())
-    gd = float((tf.flat_grad - tg.flat_grad).norm() / tg.flat_grad.norm())
-    gmax = float((tf.flat_grad - tg.flat_grad).abs().max() / tg.flat_grad.abs().max())
-    print(f"{name} pos_only={pos_only}: nll rel {e_nll:.2e}; gradient bucket |d|_2/|g|_2 {gd:.2e}, max|d|/max|g| {gmax:.2e}")
-    assert e_nll <= 2e-6 and gd <= 2e-6 and gmax <= 2e-6
-    K = 3
-    for k in range(K):
-        assert abs(float(terms[k].mean()) / (tf.loss.scales[k] + 1e-4) - info_g[f"error_t_{k}"]) <= 2e-6 * max(1.0, abs(info_g[f"error_t_{k}"]))
-        assert abs(float(terms[K + k].mean()) - info_g[f"unorm_error_t_{k}"]) <= 2e-6 * max(1.0, abs(info_g[f"unorm_error_t_{k}"]))
+    _fused_against_autograd(lambda fused: _trainer(c, dev, fused, pos_only), lambda: c.reps(torch.float32, dev), cond, t_int, draws,
+                            f"{name} pos_only={pos_only}")
+
+
+def test_fused_equals_autograd_off_the_fixtures():
+    """The same comparison on a batch no fixture has (tests/_loss_cases.py): ragged groups, two t = 0 samples under precision = 0.05
+    (sigma_0 = 0.2236: the discretised likelihoods are not all 0 or 1), fixed_idx = [1], norm_biases = (0, 0.5, 0), feature noise on -
+    the options as DDPMTrainer hands them to oard_loss_prepare / oard_loss_terms (tests/test_loss_kernels.py drives those directly).
+    The narrow width pair, one layer, synthetic weights."""
+    import _loss_cases as lc
+    from oareactdiff_amd.dynamics import EGNNDynamics
+    from oareactdiff_amd.spec import state_spec, synthetic_state_dict
+    from oareactdiff_amd.trainer import DDPMTrainer
+    dev = torch.device("cuda:0")
+    cfg = dict(pos_require_grad=False, cutoff=5.0, num_layers=1, hidden_channels=32, num_radial=8, in_hidden_channels=8)
+    b = lc.Batch(lc.TRAINER)
+    t_list, precision, biases, pos_only, fixed_mask = lc.TRAINER_CASE
+    assert (t_list, precision, biases, pos_only, lc.FIXED[fixed_mask]) == ([0, 500, 0], 0.05, (0.0, 0.5, 0.0), 0, [1])
+    sd = synthetic_state_dict(state_spec(cfg, b.node_nfs, 1), cfg, seed=42)
+
+    def trainer(fused):
+        dyn = EGNNDynamics(model_config=dict(cfg), fragment_names=["R", "TS", "P"], node_nfs=b.node_nfs, edge_nf=0, condition_nf=1, device=dev)
+        dyn.load_state_dict(sd, strict=True)
+        return DDPMTrainer(dyn, timesteps=lc.T, precision=precision, norm_values=lc.NORM_VALUES, norm_biases=biases, scales=lc.SCALES,
+                           pos_only=bool(pos_only), fixed_idx=lc.FIXED[fixed_mask], fused=fused)
+
+    def reps():
+        return [{"size": s.to(dev), "pos": p.to(dev), "one_hot": o.to(dev), "charge": c.to(dev), "mask": m.to(dev)}
+                for s, p, o, c, m in zip(b.sizes, b.pos, b.one_hot, b.charge, b.masks)]
+
+    def draws():
+        draw = b.draw(torch.float32)
+        return lambda shape: draw(shape).to(dev)
+    t_int = torch.tensor(t_list, dtype=torch.float32, device=dev).view(-1, 1)
+    _fused_against_autograd(trainer, reps, torch.zeros(b.B, 1, device=dev), t_int, draws, "off the fixtures")
 
 
 def test_fused_step_runs_and_moves_the_weights():
