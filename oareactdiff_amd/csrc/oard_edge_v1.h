@@ -574,12 +574,16 @@ struct EquiStream {
 // al: the inner rows inside the cutoff (ActList; round 5).  Column c of the launch is list entry c; rows outside the cutoff are not
 // touched at all - their q is exactly zero in the reference and nobody reads it (the node stage walks the same list).  The grid is
 // sized for A (the host does not know n_act); workgroups behind the list end return at once.
+// skip_mid (wave-uniform; inference only, never with TRAIN): the launch is layer 0, whose vector state is exactly zero - the middle third
+// of q (th = 1: the factor of vec[src], leftnet.py:263-270) only ever multiplies zeros, so its HT slots are neither computed nor stored
+// and the node stage does not read them.  The packed stream is unchanged: the executed slots are 3 tt + {0, 2}, the prefetch names the
+// NEXT EXECUTED slot's group, and the slab parity counts executed phases (`p`), not stream positions.
 template <class D, int WAVES, bool TRAIN>
 __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const float* __restrict__ stream,
                                                              const float* __restrict__ dp0b,
                                                              const float* __restrict__ ew, const float* __restrict__ rbuf,
                                                              float* __restrict__ qbuf, float* __restrict__ zd1,
-                                                             float* __restrict__ cdbuf, ActList al) {
+                                                             float* __restrict__ cdbuf, ActList al, int skip_mid) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using S = EquiStream<D>;
     constexpr int WB = D::WB, D1T = D::D1T, RB = D::RB, HT = D::HT, G1 = S::G1, G2 = S::G2;
@@ -589,10 +593,15 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const f
     SlabPrefetch<WAVES, S::SLAB, 0, 3> pf;
     pf.wave = wave;
     pf.lane_off = (unsigned)lane * 16u;              // LDS-DMA source = uniform chunk address (SGPR pair) + this 32-bit lane offset
-    auto pf_begin = [&](int p) {
-        const int start = p < WB ? p * G1 : S::C1 + (p - WB) * G2;
-        pf.begin(stream, smem, p, start, p >= S::NPH ? 0 : (p < WB ? G1 : G2));
+    const bool skip = !TRAIN && skip_mid != 0;       // (TRAIN tapes every third of cd for the backward pass: the flag cannot reach it)
+    // ph = the phase that will read the slab (its parity picks the slab); T1: stream group ph, T2: stream group WB + slot
+    auto pf_begin = [&](int ph) {
+        pf.begin(stream, smem, ph, ph * G1, G1);
     };
+    auto pf_begin_t2 = [&](int ph, int slot) {
+        pf.begin(stream, smem, ph, S::C1 + slot * G2, slot < S::NG2 ? G2 : 0);
+    };
+    auto next_slot = [&](int i) -> int { return i + ((skip && i % 3 == 0) ? 2 : 1); };    // slot executed after slot i (th = 1 left out)
     auto hook = [&]() { pf.tick(); };
     auto A = [&](int p, int j) -> f4 {
         return *reinterpret_cast<const f4*>(smem + ((size_t)(p & 1) * S::SLAB + j) * 256 + lane * 4);
@@ -619,7 +628,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const f
     for (int b = 0; b < WB; ++b, ++p) {
         phase_barrier();
         const f4 x = xn;
-        pf_begin(p + 1);
+        if (b + 1 < WB) pf_begin(p + 1); else pf_begin_t2(p + 1, 0);
         if (b + 1 < WB) xn = ld_f4(erow + 16 * (b + 1));
         chain_kouter<D1T>(SL(p), 0, x, d1, hook);
         pf.flush();
@@ -643,7 +652,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const f
             st_f4(qrow + pend_off, pend);
             if (TRAIN) st_f4(cdrow + pend_off, pendc);
         }
-        pf_begin(p + 1);
+        pf_begin_t2(p + 1, next_slot(i));
         const int tt = i / 3, th = i - 3 * tt;
         f4 cd, cr;
         if (decltype(rows4)::value) {                          // the 13th tile of every third: 4 real rows, 4x4x1 MFMAs
@@ -661,8 +670,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const f
         ++p;
     };
     constexpr int N_FULL = S::ROWS4 ? S::NG2 - 3 : S::NG2;
-    for (int i = 0; i < N_FULL; ++i) t2_phase(i, std::false_type{});
-    for (int i = N_FULL; i < S::NG2; ++i) t2_phase(i, std::true_type{});
+    for (int i = 0; i < N_FULL; i = next_slot(i)) t2_phase(i, std::false_type{});
+    for (int i = N_FULL; i < S::NG2; i = next_slot(i)) t2_phase(i, std::true_type{});
     st_f4(qrow + pend_off, pend);
     if (TRAIN) st_f4(cdrow + pend_off, pendc);
 }

@@ -78,6 +78,8 @@ int g_auto_small = 4;       // 1: small launches use the 4-wave workgroups (one 
                             //    fill the chip anyway finishes sooner when its waves do not share a SIMD (B <= 8 reactions: -25 %)
 int g_npb = 0;              // nodes per workgroup of the node stages (0 = auto, see oard_topology_create)
 int g_poison = 0;           // 1: fill the workspace with NaN bit patterns before every forward (tests: nothing may depend on its contents)
+int g_equi_l0_skip = 1;     // 0: layer 0 runs the whole EquiMessage like every other layer (A/B and tests; see forward_impl, l0_skip)
+int g_equi_l0_taken = 0;    // did the last forward take that shortcut (tests: oard_debug_option("equi_l0_taken", 0) == OARD_OK)
 int g_parts = 0;            // sub-batches per topology (0 = auto: 4 for B >= 32, 2 for B >= 16, else 1)
 int g_small_split = 128;     // EquiMessage latency kernel: launches of <= this many 16-edge tiles run one launch per dense stage
                             // (a workgroup = 16 edges x 8 output tiles); 0 = never
@@ -465,12 +467,23 @@ int launch_gcl_v1(int prec, int variant, int conc, const TopoDev& tp, const floa
     if (first) return launch_gcl_v1s<D, false, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, A, E, ew_in, ew_out, mbuf, tape, st);
     return launch_gcl_v1s<D, true, false>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, A, E, ew_in, ew_out, mbuf, tape, st);
 }
-#define EQUI_CASE(id, WV_) case id: { \
+// the EquiMessage edge kernel an inference launch of this size runs: 2 / 1 = the streamed fp32 kernel in its 8- / 4-wave shape, 4 = a
+// latency kernel, 5 = the split-precision kernel (launch_equi_v1 dispatches on it; forward_impl asks it whether layer 0 may leave out
+// the middle third of q, which only the 8-wave streamed kernel does)
+static int equi_v1_shape(int prec, int variant, int conc, long long A, const float* d1s) {
+    if (variant == 2 && cdiv(A, 16) * conc <= 512LL * g_auto_small) variant = 1;
+    if ((variant == 2 || variant == 1) && cdiv(A, 16) * conc <= 512LL * g_auto_tiny) variant = 4;
+    if (variant == 2 && (prec & OARD_PREC_EQUI_BF16X3) && d1s) variant = 5;
+    return variant;
+}
+#define EQUI_CASE(id, WV_, SKIP_) case id: { \
         LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, WV_, false>), cdiv(tp.A, 16 * WV_), WV_ * 64, (EquiStream<D>::LDS_BYTES), st, \
-                   tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al); return OARD_OK; }
+                   tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al, SKIP_); return OARD_OK; }
+// skip_mid: layer 0 of an inference forward whose node stage is the layer-0 form of k_equi_node_v1 (forward_impl: l0_skip) - the 8-wave
+// streamed kernel leaves out the middle third of q; every other kernel ignores it
 template <class D>
 int launch_equi_v1(int prec, int variant, int conc, const TopoDev& tp, const float* wb, const LayerOff& lo, const float* stream, const float* dp0b, const float* ew,
-                   const float* rbuf, float* qbuf, float* zd1, float* cd, hipStream_t st, float* d1s = nullptr, ActList al = ActList{}) {
+                   const float* rbuf, float* qbuf, float* zd1, float* cd, hipStream_t st, float* d1s = nullptr, ActList al = ActList{}, bool skip_mid = false) {
     // (the latency kernels run every inner row: their q is zero on the rows outside the cutoff, which the node stage does not read when
     // it walks the list; the throughput kernels of both precisions take the list)
     if (zd1 && (prec & OARD_PREC_TRAIN_BF16X3) && d1s) {      // training-mode forward in split precision (optional)
@@ -480,11 +493,11 @@ int launch_equi_v1(int prec, int variant, int conc, const TopoDev& tp, const flo
     }
     if (zd1) {                   // training-mode forward
         LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 8, true>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiStream<D>::LDS_BYTES), st,
-                   tp, stream, dp0b, ew, rbuf, qbuf, zd1, cd, ActList{});
+                   tp, stream, dp0b, ew, rbuf, qbuf, zd1, cd, ActList{}, 0);
         return OARD_OK;
     }
-    if (variant == 2 && cdiv(tp.A, 16) * conc <= 512LL * g_auto_small) variant = 1;
-    if ((variant == 2 || variant == 1) && cdiv(tp.A, 16) * conc <= 512LL * g_auto_tiny) variant = 4;
+    variant = equi_v1_shape(prec, variant, conc, tp.A, d1s);
+    if (skip_mid && variant != 2) return OARD_EINVAL;        // (forward_impl asked the same function)
     if (variant == 4) {          // latency kernel: 8 waves share 16 edges
         if (t_small.a && cdiv(tp.A, 16) * conc <= g_small_split) {   // stage-split latency path: 2 launches, few tiles only
             const long long tiles = cdiv(tp.A, 16);
@@ -498,14 +511,14 @@ int launch_equi_v1(int prec, int variant, int conc, const TopoDev& tp, const flo
                    tp, wb, lo, ew, rbuf, qbuf);
         return OARD_OK;
     }
-    if (variant == 2 && (prec & OARD_PREC_EQUI_BF16X3) && d1s) {      // split precision (oard_edge_b3.h): the throughput shape only
+    if (variant == 5) {          // split precision (oard_edge_b3.h): the throughput shape only
         LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_b3<D>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiB3Stream<D>::LDS_BYTES), st, tp, wb + lo.equi_b3,
                    dp0b, wb + lo.dp2b, ew, rbuf, qbuf, d1s, nullptr, nullptr, al);
         return OARD_OK;
     }
     switch (variant) {
-        EQUI_CASE(1, 4)
-        EQUI_CASE(2, 8)
+        EQUI_CASE(1, 4, 0)
+        EQUI_CASE(2, 8, skip_mid ? 1 : 0)
         default: return OARD_EINVAL;
     }
 }
@@ -672,19 +685,27 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
                        s, vcur, v2buf, scal, vdot);
             } else return OARD_EINVAL;
         } else {
+            // layer 0 of an inference forward: vec is exactly zero there, so the third of q that only multiplies vec[src] is neither computed
+            // (8-wave streamed fp32 edge kernel) nor gathered (large-batch node stage) - both or neither, the node stage must not read what
+            // the edge kernel did not write.  The training-mode forward tapes that third of dir_proj's output for the backward pass.
+            const bool l0_skip = l == 0 && !train && g_equi_l0_skip && A > 0 && nv1 && !rows &&
+                                 equi_v1_shape(c->precision, equi_variant, topo->conc, A, (const float*)(ws + w.d1s)) == 2;
+            if (l == 0) g_equi_l0_taken = l0_skip;
             if (A > 0) {
                 int rc = launch_equi_v1<D>(c->precision, equi_variant, topo->conc, tp, wb, lo, wb + lo.equi_stream, wb + lo.dp0b, ew_out, rbuf, vmsg,
                                            train ? (float*)(tape + to.zd1[l]) : nullptr, train ? (float*)(tape + to.cd[l]) : nullptr, st,
-                                           (float*)(ws + w.d1s), al);
+                                           (float*)(ws + w.d1s), al, l0_skip);
                 if (rc != OARD_OK) return rc;
             }
-#define EQUI_NODE_V1(ROWS_, XC_) LAUNCH(F_NODE, (k_equi_node_v1<D, NW, ROWS_, XC_>), gN16, NW * 64, st, tp, wb, lo, (const float*)vmsg, \
+#define EQUI_NODE_V1(D_, ROWS_, XC_) LAUNCH(F_NODE, (k_equi_node_v1<D_, NW, ROWS_, XC_>), gN16, NW * 64, st, tp, wb, lo, (const float*)vmsg, \
                        (const float*)xq, (const float*)geo, (const float*)x1, (const float*)s_mid_at(l), s_at(l + 1), (const float*)vcur, vnext, \
                        train ? (float*)(tape + to.s_a[l]) : nullptr, train ? (float*)(tape + to.vec_a[l]) : nullptr, al)
             if (nv1 && rows) {
-                if (lo.xcross) EQUI_NODE_V1(true, true); else EQUI_NODE_V1(true, false);
+                if (lo.xcross) EQUI_NODE_V1(D, true, true); else EQUI_NODE_V1(D, true, false);
+            } else if (nv1 && l0_skip) {
+                if (lo.xcross) EQUI_NODE_V1(Layer0<D>, false, true); else EQUI_NODE_V1(Layer0<D>, false, false);
             } else if (nv1) {
-                if (lo.xcross) EQUI_NODE_V1(false, true); else EQUI_NODE_V1(false, false);
+                if (lo.xcross) EQUI_NODE_V1(D, false, true); else EQUI_NODE_V1(D, false, false);
             } else if constexpr (kV0) {
                 LAUNCH(F_NODE, (k_equi_agg_v1<D>), gN, 256, st, tp, wb, lo, (const float*)vmsg, (const float*)xq,
                        (const float*)geo, (const float*)x1, s, (const float*)vcur, vnext, v2buf, scal, vdot);
@@ -2308,6 +2329,8 @@ int oard_debug_option(const char* name, int value) {
     if (strcmp(name, "experiments") == 0) return kV0 ? OARD_OK : OARD_EINVAL;      // query: is this an experiment build?
     if (strcmp(name, "gcl_skip") == 0) { g_gcl_skip = value; return OARD_OK; }
     if (strcmp(name, "equi_skip") == 0) { g_equi_skip = value; return OARD_OK; }
+    if (strcmp(name, "equi_l0_skip") == 0) { g_equi_l0_skip = value; return OARD_OK; }
+    if (strcmp(name, "equi_l0_taken") == 0) return g_equi_l0_taken ? OARD_OK : OARD_EINVAL;      // query: did the last forward skip it?
     if (strcmp(name, "gcl_persist") == 0) { g_gcl_persist = value; return OARD_OK; }
     if (strcmp(name, "gcl_grid") == 0) { g_gcl_grid = value; return OARD_OK; }
     if (strcmp(name, "skip_families") == 0) { g_skip_families = value; return OARD_OK; }

@@ -526,6 +526,15 @@ OARD_DEV float lin3u1(const float* l3s, const float* __restrict__ p, float x) {
 // =====================================================================================================
 // XC: reflect_equiv = False - the message carries x (x) coord_cross as well (leftnet.py:268-272); its own instantiation, so
 // that the production kernel's register budget is untouched
+// D = Layer0<Dims<...>> (large-batch gather only): layer 0 of an inference forward.  The vector state entering it is exactly zero, so
+// vec[src] * a2 adds nothing and the edge kernel has not written the middle third of q (k_equi_edge_v1, skip_mid): neither that third of
+// q and of xq[src] nor vec_in[src] is loaded.  A zero takes their place in the unchanged expressions, so the sums are the same bit for
+// bit (up to the sign of an exact zero) however the compiler contracts the products.  Its own instantiation, selected through the
+// dimensions type: the instantiations of the other layers keep their names and their register budget (36 bytes of scratch at the
+// 128-register cap; a run-time flag costs 8 more, and loads from scratch inside the gather loop).
+template <class D> struct Layer0 : D {};
+template <class D> struct is_layer0 { static constexpr bool value = false; };
+template <class D> struct is_layer0<Layer0<D> > { static constexpr bool value = true; };
 template <class D, int WAVES, bool ROWS = false, bool XC = false>
 __global__ __launch_bounds__(WAVES * 64) void k_equi_node_v1(TopoDev tp, const float* __restrict__ wb, LayerOff lo,
                                                              const float* __restrict__ qbuf, const float* __restrict__ xq,
@@ -534,6 +543,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_node_v1(TopoDev tp, const f
                                                              float* __restrict__ vec_out,
                                                              float* __restrict__ sa_out, float* __restrict__ va_out /* training tape: state after the aggregation, or NULL */,
                                                              ActList al /* inner rows inside the cutoff: the gather walks this list (NULL: every row) */) {
+    constexpr bool L0 = is_layer0<D>::value;
+    static_assert(!(L0 && ROWS), "the layer-0 form exists for the large-batch gather only");
     // s: scalar state entering the stage (s_mid), s_out: the state leaving it - the same buffer in inference (every element is read and
     // later written by the same lane), the tape slots s_mid[l] / s_in[l + 1] in training
     constexpr int HT = D::HT;
@@ -623,6 +634,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_node_v1(TopoDev tp, const f
         };
 #pragma unroll
         for (int i = 0; i < 2; ++i) entry(i, mnext[i], rnext[i]);
+        float zero1 = 0.f;
+        if (L0) asm volatile("" : "+v"(zero1));          // opaque to the optimiser: the expressions keep their shape
+        const f4 zero4 = {zero1, zero1, zero1, zero1};
         for (int k = 0; !ROWS && k < mx; k += 2) {
             f4 q0[2], q1[2], q2[2], y0[2], y1[2], y2[2], w0[2], w1[2], w2[2];
             float gx[2], gy[2], gz[2], cx[2], cy[2], cz[2];
@@ -637,13 +651,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_node_v1(TopoDev tp, const f
                 const float* g = geo + a * GEO_STRIDE;
                 gx[i] = g[2]; gy[i] = g[3]; gz[i] = g[4];
                 cx[i] = XC ? g[5] : 0.f; cy[i] = XC ? g[6] : 0.f; cz[i] = XC ? g[7] : 0.f;
-                q0[i] = ld_blk(qbuf, a, 3 * D::HP, t, nb.lane); q1[i] = ld_blk(qbuf, a, 3 * D::HP, HT + t, nb.lane);
+                q0[i] = ld_blk(qbuf, a, 3 * D::HP, t, nb.lane); q1[i] = L0 ? zero4 : ld_blk(qbuf, a, 3 * D::HP, HT + t, nb.lane);
                 q2[i] = ld_blk(qbuf, a, 3 * D::HP, 2 * HT + t, nb.lane);
-                y0[i] = ld_blk(xq, m, 3 * D::HP, t, nb.lane); y1[i] = ld_blk(xq, m, 3 * D::HP, HT + t, nb.lane);
+                y0[i] = ld_blk(xq, m, 3 * D::HP, t, nb.lane); y1[i] = L0 ? zero4 : ld_blk(xq, m, 3 * D::HP, HT + t, nb.lane);
                 y2[i] = ld_blk(xq, m, 3 * D::HP, 2 * HT + t, nb.lane);
-                w0[i] = ld_blk(vec_in, (size_t)m * 3 + 0, D::HP, t, nb.lane);
-                w1[i] = ld_blk(vec_in, (size_t)m * 3 + 1, D::HP, t, nb.lane);
-                w2[i] = ld_blk(vec_in, (size_t)m * 3 + 2, D::HP, t, nb.lane);
+                w0[i] = L0 ? zero4 : ld_blk(vec_in, (size_t)m * 3 + 0, D::HP, t, nb.lane);
+                w1[i] = L0 ? zero4 : ld_blk(vec_in, (size_t)m * 3 + 1, D::HP, t, nb.lane);
+                w2[i] = L0 ? zero4 : ld_blk(vec_in, (size_t)m * 3 + 2, D::HP, t, nb.lane);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
