@@ -57,6 +57,15 @@ def check(rc: int, what: str) -> None:
         raise OardError(f"{what} failed: {ERRORS.get(rc, rc)}")
 
 
+def ptr_array(tensors, n=None):
+    """`void *[n]` of the tensors' addresses for a `POINTER(c_void_p)` argument (`n`: the list's length unless given).  A None entry is
+    NULL; None for the whole list is NULL."""
+    if tensors is None:
+        return None
+    ptrs = [None if t is None else t.data_ptr() for t in tensors]
+    return (C.c_void_p * (len(ptrs) if n is None else n))(*ptrs)
+
+
 _lib = None
 
 

@@ -35,6 +35,72 @@ def _xavier_names(name: str) -> bool:
     return name.endswith(keys)
 
 
+class _CallBuffers:
+    """What one network call scribbles on: the workspace, the grow-only tape of the fused trainer, the scratch of the backward sweep and
+    the sticky NaN flag.  A module owns one set (`EGNNDynamics._call_buffers`); whoever runs a second call beside the module's own -
+    DDPMTrainer's second micro-batch - owns a second set and hands it to `_run_forward_train` / `training.Sweep`.  Every buffer is
+    reallocated when it is too small or sits on another device, and never shrinks."""
+    __slots__ = ("ws", "tape_buf", "scratch_buf", "nan_seen")
+
+    def __init__(self) -> None:
+        self.ws = self.tape_buf = self.scratch_buf = self.nan_seen = None
+
+    @staticmethod
+    def _fits(buf: Optional[Tensor], need: int, dev) -> bool:
+        return buf is not None and buf.numel() >= need and buf.device == dev
+
+    def workspace(self, need: int, dev) -> Tensor:
+        if not self._fits(self.ws, need, dev):
+            self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self.ws
+
+    def tape(self, nbytes: int, dev) -> Tensor:
+        """`nbytes` of ONE grow-only buffer (1/8 headroom): batch layouts of changing size would otherwise have the allocator carve
+        multi-GB blocks of ever new sizes."""
+        if not self._fits(self.tape_buf, nbytes, dev):
+            self.tape_buf = None                                          # released before its successor is carved
+            self.tape_buf = torch.empty(nbytes + nbytes // 8, dtype=torch.uint8, device=dev)
+        return self.tape_buf[:nbytes]
+
+    def scratch(self, need: int, dev) -> Tensor:
+        if not self._fits(self.scratch_buf, need, dev):
+            self.scratch_buf = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self.scratch_buf
+
+    def note(self, status: Tensor) -> None:
+        """OR a call's device-side status into the sticky flag (no host sync)."""
+        if self.nan_seen is None or self.nan_seen.device != status.device:
+            self.nan_seen = torch.zeros(2, dtype=torch.int32, device=status.device)
+        self.nan_seen.bitwise_or_(status)
+
+    def reset(self) -> None:
+        if self.nan_seen is not None:
+            self.nan_seen.zero_()
+
+
+class _TensorKeyCache(OrderedDict):
+    """LRU of at most `cap` objects keyed by the address, version and shape of the tensors they were built from.  An entry keeps those
+    tensors alive (`key_tensors`), so that the caching allocator cannot hand their storage to a different layout of the same size while
+    the entry exists."""
+
+    def __init__(self, cap: int = 8) -> None:
+        super().__init__()
+        self.cap = cap
+
+    def lookup(self, tensors: Tuple[Optional[Tensor], ...], extra: tuple, build):
+        key = tuple((0, 0, ()) if t is None else (t.data_ptr(), t._version, t.shape) for t in tensors) + extra
+        hit = self.get(key)
+        if hit is not None:
+            self.move_to_end(key)
+            return hit
+        hit = build()
+        hit.key_tensors = tensors
+        self[key] = hit
+        while len(self) > self.cap:
+            self.popitem(last=False)
+        return hit
+
+
 class EGNNDynamics(nn.Module):
     def __init__(
         self,
@@ -153,19 +219,36 @@ class EGNNDynamics(nn.Module):
         #: None: fp32 unless OARD_TRAIN_B3=1.
         self.train_edge_precision: Optional[str] = None
         self.last_status: Optional[Tensor] = None
-        self.nan_seen: Optional[Tensor] = None
-        self._packed: Optional[Tensor] = None
-        self._packed_key = None
-        self._packed_bwd: Optional[Tensor] = None
-        self._packed_bwd_key = None
-        self._topo_cache: "OrderedDict[tuple, _Topology]" = OrderedDict()
-        self._train_topo_cache: "OrderedDict[tuple, object]" = OrderedDict()
-        self._ws: Optional[Tensor] = None
+        self._call_buffers = _CallBuffers()           # `_ws` and `nan_seen` below are views onto it
+        self._packs: Dict[bool, list] = {}            # backward? -> [key, packed weights]
+        self._slots = None                            # (module tree, (owning module, attribute) per tensor): _ordered_tensors
+        self._topo_cache = _TensorKeyCache(8)
+        self._train_topo_cache = _TensorKeyCache(4)
+        self.grad_inplace = False                     # DDPMTrainer: the sweep accumulates into the parameters' .grad (training.DynamicsFunction)
         self._last_topo: Optional["_Topology"] = None
         #: "auto": the complete graph per sample runs the production kernels, any other edge list the general path (csrc/oard_general.h);
         #: "general": every inference call runs the general path (tests: two independent implementations of the same network)
         self.edge_list_path = "auto"
         self._warned_unbuilt = False
+
+    @property
+    def _ws(self) -> Optional[Tensor]:
+        return self._call_buffers.ws
+
+    @_ws.setter
+    def _ws(self, t: Optional[Tensor]) -> None:
+        self._call_buffers.ws = t
+
+    @property
+    def nan_seen(self) -> Optional[Tensor]:
+        return self._call_buffers.nan_seen
+
+    @nan_seen.setter
+    def nan_seen(self, t: Optional[Tensor]) -> None:
+        self._call_buffers.nan_seen = t
+
+    def reset_nan_seen(self) -> None:
+        self._call_buffers.reset()
 
     # ------------------------------------------------------------------------------------------
     def _config(self) -> _capi.OardConfig:
@@ -207,7 +290,7 @@ class EGNNDynamics(nn.Module):
         1.5 - 4 ms, and a training step asks five times); the tensors themselves are looked up afresh every call, so parameters that
         were re-assigned or re-loaded are seen."""
         tree = tuple(id(m) for m in self.modules())
-        slots = self.__dict__.get("_slots")
+        slots = self._slots
         if slots is None or slots[0] != tree:
             pairs = []
             for name in self._spec:
@@ -216,7 +299,7 @@ class EGNNDynamics(nn.Module):
                 for p in parts[:-1]:
                     mod = mod[int(p)] if (p.isdigit() and isinstance(mod, nn.ModuleList)) else getattr(mod, p)
                 pairs.append((mod, parts[-1]))
-            slots = self.__dict__["_slots"] = (tree, pairs)
+            slots = self._slots = (tree, pairs)
         out: List[Tensor] = []
         for mod, attr in slots[1]:
             t = mod._parameters.get(attr)
@@ -225,12 +308,15 @@ class EGNNDynamics(nn.Module):
             out.append(t if t is not None else getattr(mod, attr))
         return out
 
-    def _get_packed(self, cfg: _capi.OardConfig, stream: int) -> Tensor:
+    def _pack(self, bwd: bool, cfg: _capi.OardConfig, stream: int) -> Tensor:
+        """The packed weight stream of the forward kernels, or (`bwd`) the transposed one of the backward edge kernels: repacked when a
+        parameter's address or version changes, the forward one also with `cfg.precision`."""
         tensors = self._ordered_tensors()
+        key = tuple((t.data_ptr(), t._version) for t in tensors) + (() if bwd else (cfg.precision,))
+        slot = self._packs.get(bwd)
+        if slot is not None and slot[0] == key:
+            return slot[1]
         L = _capi.lib()
-        key = tuple((t.data_ptr(), t._version) for t in tensors) + (cfg.precision,)
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
         dev = tensors[0].device
         for t in tensors:
             if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
@@ -238,27 +324,26 @@ class EGNNDynamics(nn.Module):
         n = L.oard_param_count(C.byref(cfg))
         if n != len(tensors):
             raise _capi.OardError(f"parameter count mismatch: library expects {n}, module has {len(tensors)}")
-        nbytes = L.oard_packed_bytes(C.byref(cfg))
+        size, pack, what = ((L.oard_packed_bwd_bytes, L.oard_pack_weights_bwd, "oard_pack_weights_bwd") if bwd else
+                            (L.oard_packed_bytes, L.oard_pack_weights, "oard_pack_weights"))
+        nbytes = size(C.byref(cfg))
         packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
-        _capi.check(L.oard_pack_weights(C.byref(cfg), ptrs, n, packed.data_ptr(), nbytes, stream), "oard_pack_weights")
-        self._packed, self._packed_key = packed, key
+        _capi.check(pack(C.byref(cfg), _capi.ptr_array(tensors), n, packed.data_ptr(), nbytes, stream), what)
+        self._packs[bwd] = [key, packed]
         return packed
+
+    def _get_packed(self, cfg: _capi.OardConfig, stream: int) -> Tensor:
+        return self._pack(False, cfg, stream)
 
     def _get_packed_bwd(self, cfg: _capi.OardConfig, stream: int) -> Tensor:
         """Transposed weight streams of the backward edge kernels (repacked when a parameter changes)."""
-        tensors = self._ordered_tensors()
-        key = tuple((t.data_ptr(), t._version) for t in tensors)
-        if self._packed_bwd is not None and key == self._packed_bwd_key:
-            return self._packed_bwd
-        L = _capi.lib()
-        n = L.oard_param_count(C.byref(cfg))
-        nbytes = L.oard_packed_bwd_bytes(C.byref(cfg))
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=tensors[0].device)
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
-        _capi.check(L.oard_pack_weights_bwd(C.byref(cfg), ptrs, n, packed.data_ptr(), nbytes, stream), "oard_pack_weights_bwd")
-        self._packed_bwd, self._packed_bwd_key = packed, key
-        return packed
+        return self._pack(True, cfg, stream)
+
+    def invalidate_packed(self) -> None:
+        """The weights changed behind torch's version counters (the fused optimiser kernel): the next call repacks them.  The blobs
+        themselves stay alive until then."""
+        for slot in self._packs.values():
+            slot[0] = None
 
     def _param_names(self) -> List[str]:
         """Canonical (first) state-dict name of every distinct trainable parameter, in state-dict order."""
@@ -293,21 +378,28 @@ class EGNNDynamics(nn.Module):
     def _get_topology(self, cfg, edge_index: Tensor, n_frag_switch: Tensor, combined_mask: Tensor,
                       stream: int, force_general: bool = False) -> "_Topology":
         force_general = force_general or self.edge_list_path == "general"
-        key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape),
-               n_frag_switch.data_ptr(), n_frag_switch._version, combined_mask.data_ptr(), combined_mask._version,
-               combined_mask.numel(), force_general)
-        topo = self._topo_cache.get(key)
-        if topo is not None:
-            self._topo_cache.move_to_end(key)
-            return topo
-        topo = _Topology(cfg, edge_index, n_frag_switch, combined_mask, stream, force_general=force_general)
-        # the key is made of addresses and versions: the entry keeps the three tensors alive so that the caching
-        # allocator cannot hand their storage to a different layout of the same size while the entry exists
-        topo.key_tensors = (edge_index, n_frag_switch, combined_mask)
-        self._topo_cache[key] = topo
-        while len(self._topo_cache) > 8:
-            self._topo_cache.popitem(last=False)
-        return topo
+        return self._topo_cache.lookup((edge_index, n_frag_switch, combined_mask), (force_general,), lambda: _Topology(
+            cfg, edge_index, n_frag_switch, combined_mask, stream, force_general=force_general))
+
+    def _inputs(self, topo, xh: List[Tensor], t: Tensor, conditions: Tensor, dev, detach: bool = False):
+        """The call's operands as the library takes them -> (xs, tt, t_scalar, cond): contiguous float32 rows per object (`detach`: cut
+        from the caller's autograd graph, the training path), the time argument, the conditions."""
+        xs = []
+        for k in range(len(self.node_nfs)):
+            x = xh[k].detach() if detach else xh[k]
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                x = x.contiguous().float()
+            if x.shape != (topo.obj_counts[k], self.node_nfs[k]):
+                raise _capi.OardError(f"xh[{k}] has shape {tuple(x.shape)}, expected "
+                                      f"{(topo.obj_counts[k], self.node_nfs[k])}")
+            xs.append(x)
+        tt, t_scalar = self._time_argument(t, dev, topo.max_sample_id)
+        cond = None
+        if self.condition_nf > 0:
+            cond = conditions.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if cond.shape[0] <= topo.max_sample_id or cond.shape[1] != self.condition_nf:
+                raise _capi.OardError("conditions has the wrong shape")
+        return xs, tt, t_scalar, cond
 
     # ------------------------------------------------------------------------------------------
     def forward(
@@ -350,29 +442,14 @@ class EGNNDynamics(nn.Module):
                 return self._forward_train(cfg, packed, xh, edge_index, t, conditions, n_frag_switch, combined_mask, stream)
             topo = self._get_topology(cfg, edge_index, n_frag_switch, combined_mask, stream, force_general=not built)
             n_obj = len(self.node_nfs)
-            xs = []
-            for k in range(n_obj):
-                x = xh[k]
-                if x.dtype != torch.float32 or not x.is_contiguous():
-                    x = x.contiguous().float()
-                if x.shape != (topo.obj_counts[k], self.node_nfs[k]):
-                    raise _capi.OardError(f"xh[{k}] has shape {tuple(x.shape)}, expected "
-                                          f"{(topo.obj_counts[k], self.node_nfs[k])}")
-                xs.append(x)
+            xs, tt, t_scalar, cond = self._inputs(topo, xh, t, conditions, dev)
             outs = [torch.empty_like(x) for x in xs]
-            tt, t_scalar = self._time_argument(t, dev, topo.max_sample_id)
-            cond = None
-            if self.condition_nf > 0:
-                cond = conditions.detach().to(device=dev, dtype=torch.float32).contiguous()
-                if cond.shape[0] <= topo.max_sample_id or cond.shape[1] != self.condition_nf:
-                    raise _capi.OardError("conditions has the wrong shape")
             general = topo.graph is not None
             need = L.oard_graph_workspace_bytes(C.byref(cfg), topo.graph) if general else L.oard_workspace_bytes(C.byref(cfg), topo.handle)
-            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            buffers = self._call_buffers
+            ws = buffers.workspace(need, dev)
             status = torch.zeros(2, dtype=torch.int32, device=dev)
-            xp = (C.c_void_p * n_obj)(*[x.data_ptr() for x in xs])
-            op = (C.c_void_p * n_obj)(*[o.data_ptr() for o in outs])
+            xp, op = _capi.ptr_array(xs), _capi.ptr_array(outs)
             if general:
                 if self.nan_check == "replace":
                     raise _capi.OardError("nan_check='replace' is implemented for the complete-graph topology only")
@@ -380,26 +457,22 @@ class EGNNDynamics(nn.Module):
                 for tns in tensors:
                     if tns is not None and (tns.dtype != torch.float32 or not tns.is_contiguous() or tns.device != dev):
                         raise _capi.OardError("the general-edge-list path needs contiguous float32 parameters on the call's device")
-                pp = (C.c_void_p * len(tensors))(*[tns.data_ptr() if tns is not None else None for tns in tensors])
-                rc = L.oard_graph_forward(C.byref(cfg), topo.graph, pp, len(tensors), xp, tt.data_ptr(), t_scalar,
-                                          cond.data_ptr() if cond is not None else None, op, self._ws.data_ptr(), self._ws.numel(),
+                rc = L.oard_graph_forward(C.byref(cfg), topo.graph, _capi.ptr_array(tensors), len(tensors), xp, tt.data_ptr(), t_scalar,
+                                          cond.data_ptr() if cond is not None else None, op, ws.data_ptr(), ws.numel(),
                                           status.data_ptr(), stream)
                 _capi.check(rc, "oard_graph_forward")
             else:
                 rc = L.oard_forward(C.byref(cfg), topo.handle, packed.data_ptr(), xp, tt.data_ptr(), t_scalar,
-                                    cond.data_ptr() if cond is not None else None, op, self._ws.data_ptr(),
-                                    self._ws.numel(), status.data_ptr(), stream)
+                                    cond.data_ptr() if cond is not None else None, op, ws.data_ptr(), ws.numel(), status.data_ptr(), stream)
                 _capi.check(rc, "oard_forward")
             self._last_topo = topo
             self.last_status = status
             if self.nan_check != "sync":
-                if self.nan_seen is None or self.nan_seen.device != dev:
-                    self.nan_seen = torch.zeros(2, dtype=torch.int32, device=dev)
-                self.nan_seen.bitwise_or_(status)         # device-side, no sync
+                buffers.note(status)
             if self.nan_check == "replace":               # the reference's guard (:138-143) on the device: randn velocities iff the flag is set
                 noise = [torch.randn(o.shape[0], self.pos_dim, device=dev) for o in outs]
-                nz = (C.c_void_p * n_obj)(*[x.data_ptr() for x in noise])
-                _capi.check(L.oard_nan_replace(C.byref(cfg), topo.handle, status.data_ptr(), nz, op, stream), "oard_nan_replace")
+                _capi.check(L.oard_nan_replace(C.byref(cfg), topo.handle, status.data_ptr(), _capi.ptr_array(noise), op, stream),
+                            "oard_nan_replace")
             if self.nan_check == "sync" and int(status[0].item()) != 0:   # egnn_dynamics.py:138-143
                 print("Warning: detected nan in pos, resetting EGNN output to randn.")
                 for k in range(n_obj):
@@ -411,10 +484,6 @@ class EGNNDynamics(nn.Module):
                         v = v - (mean / cnt.clamp(min=1).unsqueeze(1))[idx]
                     outs[k][:, : self.pos_dim] = v
         return outs, None
-
-    def reset_nan_seen(self) -> None:
-        if self.nan_seen is not None:
-            self.nan_seen.zero_()
 
     @staticmethod
     def _time_argument(t: Tensor, dev, max_sample_id: int) -> Tuple[Tensor, int]:
@@ -439,75 +508,32 @@ class EGNNDynamics(nn.Module):
         a loader that reuses its batch tensors pays the table build once; a new layout costs ~1.5 ms of host time and no device
         synchronisation (training.TrainTopology)."""
         from . import training
-        key = (0 if edge_index is None else edge_index.data_ptr(), 0 if edge_index is None else edge_index._version,
-               () if edge_index is None else tuple(edge_index.shape),
-               n_frag_switch.data_ptr(), n_frag_switch._version, combined_mask.data_ptr(), combined_mask._version,
-               combined_mask.numel())
-        topo = self._train_topo_cache.get(key)
-        if topo is None:
-            topo = training.TrainTopology(cfg, combined_mask, n_frag_switch, stream, edge_index=edge_index, device=device)
-            topo.key_tensors = (edge_index, n_frag_switch, combined_mask)       # keep the addresses of the key alive
-            self._train_topo_cache[key] = topo
-            while len(self._train_topo_cache) > 4:
-                self._train_topo_cache.popitem(last=False)
-        else:
-            self._train_topo_cache.move_to_end(key)
-        return topo
-
-    def _train_inputs(self, topo, xh: List[Tensor], t: Tensor, conditions: Tensor, dev):
-        n_obj = len(self.node_nfs)
-        xs = []
-        for k in range(n_obj):
-            x = xh[k].detach()
-            if x.dtype != torch.float32 or not x.is_contiguous():
-                x = x.contiguous().float()
-            if x.shape != (topo.obj_counts[k], self.node_nfs[k]):
-                raise _capi.OardError(f"xh[{k}] has shape {tuple(x.shape)}")
-            xs.append(x)
-        tt, t_scalar = self._time_argument(t, dev, topo.max_sample_id)
-        cond = None
-        if self.condition_nf > 0:
-            cond = conditions.detach().to(device=dev, dtype=torch.float32).contiguous()
-            if cond.shape[0] <= topo.max_sample_id or cond.shape[1] != self.condition_nf:
-                raise _capi.OardError("conditions has the wrong shape")
-        return xs, tt, t_scalar, cond
+        return self._train_topo_cache.lookup((edge_index, n_frag_switch, combined_mask), (), lambda: training.TrainTopology(
+            cfg, combined_mask, n_frag_switch, stream, edge_index=edge_index, device=device))
 
     def _run_forward_train(self, cfg, topo, packed: Tensor, xs: List[Tensor], tt: Tensor, t_scalar: int, cond: Optional[Tensor],
-                           stream: int, reuse_tape: bool = False):
+                           stream: int, reuse_tape: bool = False, buffers: Optional[_CallBuffers] = None):
         """oard_forward_train on prepared inputs -> (outs, TrainState); no autograd involved (DDPMTrainer's fused step calls this
-        directly and feeds the closed-form loss gradient to training.backward_sweep)."""
+        directly and feeds the closed-form loss gradient to training.backward_sweep).  `buffers`: the set this call writes to (None:
+        the module's own)."""
         from . import training
         L = _capi.lib()
         dev = xs[0].device
-        n_obj = len(self.node_nfs)
+        buffers = self._call_buffers if buffers is None else buffers
         outs = [torch.empty_like(x) for x in xs]
-        need = L.oard_workspace_bytes(C.byref(cfg), topo.handle)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = buffers.workspace(L.oard_workspace_bytes(C.byref(cfg), topo.handle), dev)
         # one tape per call (it lives until that call's backward has run; the caching allocator recycles it).  reuse_tape (the fused
-        # trainer: one forward, then its backward, on one stream): ONE grow-only buffer - batch layouts of changing size would otherwise
-        # have the allocator carve multi-GB blocks of ever new sizes
+        # trainer: one forward, then its backward, on one stream): the set's grow-only buffer
         tape_bytes = L.oard_tape_bytes(C.byref(cfg), topo.handle)
-        if reuse_tape:
-            tb = getattr(self, "_tape_buf", None)
-            if tb is None or tb.numel() < tape_bytes or tb.device != dev:
-                self._tape_buf = None
-                tb = self._tape_buf = torch.empty(tape_bytes + tape_bytes // 8, dtype=torch.uint8, device=dev)
-            tape = tb[:tape_bytes]
-        else:
-            tape = torch.empty(tape_bytes, dtype=torch.uint8, device=dev)
+        tape = buffers.tape(tape_bytes, dev) if reuse_tape else torch.empty(tape_bytes, dtype=torch.uint8, device=dev)
         status = torch.zeros(2, dtype=torch.int32, device=dev)
-        xp = (C.c_void_p * n_obj)(*[x.data_ptr() for x in xs])
-        op = (C.c_void_p * n_obj)(*[o.data_ptr() for o in outs])
-        rc = L.oard_forward_train(C.byref(cfg), topo.handle, packed.data_ptr(), xp, tt.data_ptr(), t_scalar,
-                                  cond.data_ptr() if cond is not None else None, op, self._ws.data_ptr(), self._ws.numel(),
+        rc = L.oard_forward_train(C.byref(cfg), topo.handle, packed.data_ptr(), _capi.ptr_array(xs), tt.data_ptr(), t_scalar,
+                                  cond.data_ptr() if cond is not None else None, _capi.ptr_array(outs), ws.data_ptr(), ws.numel(),
                                   tape.data_ptr(), tape.numel(), status.data_ptr(), stream)
         _capi.check(rc, "oard_forward_train")
         self.last_status = status
         if self.nan_check != "sync":
-            if self.nan_seen is None or self.nan_seen.device != dev:
-                self.nan_seen = torch.zeros(2, dtype=torch.int32, device=dev)
-            self.nan_seen.bitwise_or_(status)         # device-side, no sync (DDPMTrainer reads it with the gradient norm)
+            buffers.note(status)                      # device-side, no sync (DDPMTrainer reads it with the gradient norm)
         state = training.TrainState(cfg, topo, training.Tape(cfg, topo, tape), xs, tt, bool(t_scalar), cond)
         return outs, state
 
@@ -518,7 +544,7 @@ class EGNNDynamics(nn.Module):
         dev = xh[0].device
         n_obj = len(self.node_nfs)
         topo = self._get_train_topology(cfg, edge_index, n_frag_switch, combined_mask, stream)
-        xs, tt, t_scalar, cond = self._train_inputs(topo, xh, t, conditions, dev)
+        xs, tt, t_scalar, cond = self._inputs(topo, xh, t, conditions, dev, detach=True)
 
         def run_forward():
             return self._run_forward_train(cfg, topo, packed, xs, tt, t_scalar, cond, stream)
@@ -596,6 +622,7 @@ class _Topology:
             raise _capi.OardError("combined_mask / n_frag_switch size mismatch")
         self._lib = L
         self.handle, self.graph = None, None
+        self.key_tensors = None                        # set by the cache that holds this topology (_TensorKeyCache)
         self.n_nodes = int(cm.numel())
         self.max_sample_id = int(cm.max())
         n_obj = cfg.n_obj
@@ -611,34 +638,35 @@ class _Topology:
         ei = ei.contiguous()
         # the production kernels assume the complete-per-sample graph (any ordering of its edge list: outputs are per node): verify once.
         # A layout their tables do not cover (a (sample, object) group of more than 1024 atoms) cannot be that path's either way.
-        h = C.c_void_p()
-        rc = L.oard_topology_create(C.byref(cfg), C.cast(cm.data_ptr(), C.POINTER(C.c_int64)),
-                                    C.cast(nfs.data_ptr(), C.POINTER(C.c_int64)), cm.numel(), C.byref(h))
-        complete = False
-        if rc == _capi.OARD_OK:
-            ok = torch.zeros(1, dtype=torch.int32, device=dev)
-            _capi.check(L.oard_topology_check_edge_index(h, ei.data_ptr(), ei.shape[1], ok.data_ptr(), stream),
-                        "oard_topology_check_edge_index")
-            complete = int(ok.item()) == 1
-            if complete and not force_general:
-                self.handle = h
-                self.n_edges = int(L.oard_topology_num_edges(h))
-                self.n_inner = int(L.oard_topology_num_inner_edges(h))
-                self.n_samples = int(L.oard_topology_num_samples(h))
-                return
-            L.oard_topology_destroy(h)
+        # `force_general`: no production tables, no edge check, no host read.
+        if not force_general:
+            h = C.c_void_p()
+            rc_topo = L.oard_topology_create(C.byref(cfg), C.cast(cm.data_ptr(), C.POINTER(C.c_int64)),
+                                             C.cast(nfs.data_ptr(), C.POINTER(C.c_int64)), cm.numel(), C.byref(h))
+            if rc_topo == _capi.OARD_OK:
+                ok = torch.zeros(1, dtype=torch.int32, device=dev)
+                _capi.check(L.oard_topology_check_edge_index(h, ei.data_ptr(), ei.shape[1], ok.data_ptr(), stream),
+                            "oard_topology_check_edge_index")
+                if int(ok.item()) == 1:
+                    self.handle = h
+                    self.n_edges = int(L.oard_topology_num_edges(h))
+                    self.n_inner = int(L.oard_topology_num_inner_edges(h))
+                    self.n_samples = int(L.oard_topology_num_samples(h))
+                    return
+                L.oard_topology_destroy(h)
         # not the complete graph per sample (edge_cutoff graphs, disconnected components, arbitrary lists: egnn_dynamics.py:63-72
         # accepts them all): the general-edge-list path (csrc/oard_general.h) takes the call.  One host copy of the edge list per
         # topology, like the two masks above.
         ei_host = ei.to("cpu").contiguous()
         g = C.c_void_p()
-        rc = L.oard_graph_create(C.byref(cfg), cm.data_ptr(), nfs.data_ptr(), cm.numel(), ei_host.data_ptr(), ei_host.shape[1], C.byref(g))
-        _capi.check(rc, "oard_graph_create (node ids out of range, or n_frag_switch not in ascending object blocks)")
+        rc_graph = L.oard_graph_create(C.byref(cfg), cm.data_ptr(), nfs.data_ptr(), cm.numel(), ei_host.data_ptr(), ei_host.shape[1], C.byref(g))
+        _capi.check(rc_graph, "oard_graph_create (node ids out of range, or n_frag_switch not in ascending object blocks)")
         self.graph = g
         self.n_edges = int(L.oard_graph_num_edges(g))
         self.n_inner = int((nfs[ei_host[0]] == nfs[ei_host[1]]).sum()) if ei_host.shape[1] else 0
         self.n_samples = int(torch.unique(cm).numel())
-        if complete is False and rc == _capi.OARD_OK and not force_general and L.oard_graph_is_complete(g):
+        # (not forced: the production tables were refused, or the edge check said "not complete")
+        if not force_general and L.oard_graph_is_complete(g):
             import warnings
             warnings.warn("this batch layout is outside the production kernels' tables (a (sample, object) group of more than 1024 atoms): "
                           "the complete graph is served by the general-edge-list path, which is built for parity, not throughput")

@@ -9,6 +9,7 @@ table, the NaN flag stays on the device, and the reference's four `.item()` asse
 the loop never synchronises the host with the GPU."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Callable, List, Optional, Sequence, Tuple
 
@@ -56,6 +57,8 @@ class DiffusionSampler:
         self.norm_values = tuple(norm_values)
         self.norm_biases = tuple(norm_biases)
         self._layout_cache = {}
+        self.last_x: Optional[List[Tensor]] = None         # final (normalised) state and status of the last run
+        self.last_status: Optional[Tensor] = None
         #: upper bound on the pre-drawn noise of the hipGraph-replayed loop (`sample(graph=True)` / small batches)
         self.noise_block_bytes = 64 << 20
 
@@ -106,17 +109,28 @@ class DiffusionSampler:
                 e[:, :pd].addcmul_(x[:, :pd], coef)
 
     # --------------------------------------------------------------------------------------------
-    def _step_kernel(self, topo, mode, z, eh, noise, h0, a, b, c, out, stream):
+    def _launch_step(self, topo, mode, z, eh, noise, h0, scalars, out, stream):
+        """One launch of the step kernel, then the second projection for the modes that project (0 and 4).  `scalars`: the three
+        schedule scalars as host floats (a, b, c), or a [3] device tensor (the launch a hipGraph replays)."""
         L = _capi.lib()
         cfg = self.dynamics._config()
-        n = len(self.node_nfs)
-        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts]) if ts is not None else None
+        arr = _capi.ptr_array
         first = [torch.empty_like(o) for o in out] if mode in (0, 4) else out
-        rc = L.oard_sampler_step(C.byref(cfg), topo.handle, mode, arr(z), arr(eh), arr(noise), arr(h0),
-                                 C.c_float(a), C.c_float(b), C.c_float(c), 1 if self.pos_only else 0, arr(first), stream)
-        _capi.check(rc, "oard_sampler_step")
+        head = (C.byref(cfg), topo.handle, mode, arr(z), arr(eh), arr(noise), arr(h0))
+        tail = (1 if self.pos_only else 0, arr(first), stream)
+        if isinstance(scalars, Tensor):
+            _capi.check(L.oard_sampler_step_dev(*head, scalars.data_ptr(), *tail), "oard_sampler_step_dev")
+        else:
+            _capi.check(L.oard_sampler_step(*head, *[C.c_float(v) for v in scalars], *tail), "oard_sampler_step")
         if first is not out:
             self._project_again(topo, first, h0, out, stream)
+
+    def _step_kernel(self, topo, mode, z, eh, noise, h0, a, b, c, out, stream):
+        self._launch_step(topo, mode, z, eh, noise, h0, (a, b, c), out, stream)
+
+    def _step_kernel_dev(self, topo, mode, z, eh, noise, h0, coef, out, stream):
+        """As `_step_kernel` with the schedule scalars in device memory (`coef` [3]): the launch a hipGraph replays."""
+        self._launch_step(topo, mode, z, eh, noise, h0, coef, out, stream)
 
     def _project_again(self, topo, x, h0, out, stream):
         """Second CoM projection of a mode 0 / mode 4 result: out = x - mean_group(x) on the positions, everything else copied (the
@@ -127,26 +141,10 @@ class DiffusionSampler:
         and leaves 1e-8.  The loops' own operands are CoM-free, so for them the pass changes last bits only; it is here because the
         wrappers promise a CoM-free result for ANY operands.  (The one-launch form - float64 group sums inside k_sampler_step -
         belongs to a change that re-collects the profile passes, which are tied to the kernel sources: tests/test_docs_in_step.py.)"""
-        L = _capi.lib()
-        cfg = self.dynamics._config()
-        n = len(self.node_nfs)
-        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts]) if ts is not None else None
-        rc = L.oard_sampler_step(C.byref(cfg), topo.handle, 4, arr(x), None, arr(x), arr(h0),
-                                 C.c_float(1.0), C.c_float(0.0), C.c_float(0.0), 1 if self.pos_only else 0, arr(out), stream)
+        arr = _capi.ptr_array
+        rc = _capi.lib().oard_sampler_step(C.byref(self.dynamics._config()), topo.handle, 4, arr(x), None, arr(x), arr(h0),
+                                           C.c_float(1.0), C.c_float(0.0), C.c_float(0.0), 1 if self.pos_only else 0, arr(out), stream)
         _capi.check(rc, "oard_sampler_step (second projection)")
-
-    def _step_kernel_dev(self, topo, mode, z, eh, noise, h0, coef, out, stream):
-        """As `_step_kernel` with the schedule scalars in device memory (`coef` [3]): the launch a hipGraph replays."""
-        L = _capi.lib()
-        cfg = self.dynamics._config()
-        n = len(self.node_nfs)
-        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts]) if ts is not None else None
-        first = [torch.empty_like(o) for o in out] if mode in (0, 4) else out
-        rc = L.oard_sampler_step_dev(C.byref(cfg), topo.handle, mode, arr(z), arr(eh), arr(noise), arr(h0), coef.data_ptr(),
-                                     1 if self.pos_only else 0, arr(first), stream)
-        _capi.check(rc, "oard_sampler_step_dev")
-        if first is not out:
-            self._project_again(topo, first, h0, out, stream)
 
     def _graphed_steps(self, dyn, topo, timesteps, za, draw, h0d, edge_index, conditions, n_frag_switch, combined_mask, dev,
                        step_callback=None):
@@ -221,6 +219,52 @@ class DiffusionSampler:
         torch.cuda.current_stream(dev).wait_stream(side)
         return z
 
+    @contextlib.contextmanager
+    def _run(self, n_samples: int, fragments_nodes: List[Tensor], conditions: Optional[Tensor]):
+        """What `sample` and `inpaint` do around their loops -> (dev, (masks, combined_mask, edge_index, n_frag_switch), conditions, topo,
+        stream), with the device current: the batch layout, default conditions, the module's NaN check switched to the loop's (no host
+        sync; restored on the way out) with a cleared sticky flag, and the production topology.  After a loop that ended normally the
+        flag is read - the run's single host read (`_check_nan`)."""
+        dyn = self.dynamics
+        dev = next(dyn.parameters()).device
+        if dev.type != "cuda":
+            raise _capi.OardError("DiffusionSampler needs the dynamics on a ROCm device (no CPU fallback)")
+        layout = self._layout(fragments_nodes, dev)
+        _, combined_mask, edge_index, n_frag_switch = layout
+        if conditions is None:
+            conditions = torch.zeros(n_samples, max(dyn.condition_nf, 1), device=dev)
+        conditions = conditions.to(dev)
+        old_nan = dyn.nan_check
+        dyn.nan_check = "replace" if self.on_nan == "replace" else "async"
+        dyn.reset_nan_seen()
+        try:
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                topo = dyn._get_topology(dyn._config(), edge_index, n_frag_switch, combined_mask, stream)
+                if topo.handle is None:
+                    raise _capi.OardError("the sampling loops run on the production kernels: hidden_channels / num_radial must be a built width "
+                                          "pair (OARD_DIMS=... python -m oareactdiff_amd.build) and a (sample, object) group at most 1024 atoms")
+                yield dev, layout, conditions, topo, stream
+        finally:
+            dyn.nan_check = old_nan
+        self._check_nan(dyn)
+
+    def _to_samples(self, x: List[Tensor], h0: Optional[List[Tensor]], h0_long: bool) -> List[Tensor]:
+        """The final state un-normalised into [pos | one-hot | charge] per object (en_diffusion.py:542-557, :680-683).  `pos_only`: the
+        features are `h0`'s, as integers if `h0_long` (inpaint; sample hands them back in h0's dtype)."""
+        nv, nb, pd = self.norm_values, self.norm_biases, self.pos_dim
+        n_obj = len(self.node_nfs)
+        pos = [x[k][:, :pd] * nv[0] + nb[0] for k in range(n_obj)]
+        if self.pos_only:
+            cat, charge = [h[:, :-1] for h in h0], [h[:, -1:] for h in h0]
+            if h0_long:
+                cat, charge = [c.long() for c in cat], [c.long() for c in charge]
+        else:
+            cat = [torch.nn.functional.one_hot(torch.argmax(x[k][:, pd:-1] * nv[1] + nb[1], dim=1),
+                                               self.node_nfs[k] - 4).long() for k in range(n_obj)]
+            charge = [torch.round(x[k][:, -1:] * nv[2] + nb[2]).long() for k in range(n_obj)]
+        return [torch.cat([pos[k], cat[k], charge[k]], dim=1) for k in range(n_obj)]
+
     @torch.no_grad()
     def sample(self, n_samples: int, fragments_nodes: List[Tensor], conditions: Optional[Tensor] = None,
                return_frames: int = 1, timesteps: Optional[int] = None, h0: Optional[List[Tensor]] = None,
@@ -238,81 +282,53 @@ class DiffusionSampler:
         assert 0 < return_frames <= timesteps and timesteps % return_frames == 0       # en_diffusion.py:473-475
         assert h0 is not None if self.pos_only else True
         dyn = self.dynamics
-        dev = next(dyn.parameters()).device
-        if dev.type != "cuda":
-            raise _capi.OardError("DiffusionSampler needs the dynamics on a ROCm device (no CPU fallback)")
         n_obj = len(self.node_nfs)
-        masks, combined_mask, edge_index, n_frag_switch = self._layout(fragments_nodes, dev)
-        if conditions is None:
-            conditions = torch.zeros(n_samples, max(dyn.condition_nf, 1), device=dev)
-        conditions = conditions.to(dev)
-        h0d = [h.to(device=dev, dtype=torch.float32).contiguous() for h in h0] if h0 is not None else None
-        sizes = [int(m.numel()) for m in masks]
-        old_nan = dyn.nan_check
-        dyn.nan_check = "replace" if self.on_nan == "replace" else "async"
-        dyn.reset_nan_seen()
-        try:
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                cfg = dyn._config()
-                topo = dyn._get_topology(cfg, edge_index, n_frag_switch, combined_mask, stream)
-                if topo.handle is None:
-                    raise _capi.OardError("the sampling loops run on the production kernels: hidden_channels / num_radial must be a built width "
-                                          "pair (OARD_DIMS=... python -m oareactdiff_amd.build) and a (sample, object) group at most 1024 atoms")
+        with self._run(n_samples, fragments_nodes, conditions) as (dev, layout, conditions, topo, stream):
+            masks, combined_mask, edge_index, n_frag_switch = layout
+            h0d = [h.to(device=dev, dtype=torch.float32).contiguous() for h in h0] if h0 is not None else None
+            sizes = [int(m.numel()) for m in masks]
 
-                def draw(i):
-                    if noise_fn is not None:
-                        return [x.to(device=dev, dtype=torch.float32).contiguous() for x in noise_fn(i)]
-                    return [torch.randn(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
+            def draw(i):
+                if noise_fn is not None:
+                    return [x.to(device=dev, dtype=torch.float32).contiguous() for x in noise_fn(i)]
+                return [torch.randn(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
 
-                za = [torch.empty(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
-                zb = [torch.empty_like(z) for z in za]
-                self._step_kernel(topo, 2, None, None, draw(0), h0d if self.pos_only else None, 0.0, 0.0, 1.0, za, stream)
-                t_table = torch.arange(timesteps + 1, device=dev, dtype=torch.float32) / timesteps
-                ptab = self._prior_table(timesteps, dev) if self.prior_std is not None else None
-                out_samples = [None] * return_frames
-                call = 1
-                use_graph = ((n_samples <= 8 and return_frames == 1 and not torch.cuda.is_current_stream_capturing())
-                             if graph is None else bool(graph))
-                if use_graph:
-                    assert return_frames == 1, "intermediate frames need the eager loop"
-                    za = self._graphed_steps(dyn, topo, timesteps, za, draw, h0d, edge_index, conditions, n_frag_switch,
-                                             combined_mask, dev, step_callback)
-                    call = timesteps + 1
-                for s in (reversed(range(timesteps)) if not use_graph else ()):
-                    co = self.schedule.step(s, timesteps)
-                    eps_hat, _ = dyn(za, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
-                    if ptab is not None:
-                        self._add_prior(eps_hat, za, ptab[s + 1: s + 2])
-                    self._step_kernel(topo, 0, za, eps_hat, draw(call), h0d if self.pos_only else None,
-                                      co.alpha_ts, co.c_eps, co.sigma, zb, stream)
-                    if step_callback is not None:
-                        step_callback(call)
-                    call += 1
-                    za, zb = zb, za
-                    if (s * return_frames) % timesteps == 0 and return_frames > 1:
-                        out_samples[(s * return_frames) // timesteps] = self._unnormalize_z([z.clone() for z in za])
-                fc = self.schedule.final()
-                eps_hat, _ = dyn(za, edge_index, t_table[0:1], conditions, n_frag_switch, combined_mask)
+            za = [torch.empty(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
+            zb = [torch.empty_like(z) for z in za]
+            self._step_kernel(topo, 2, None, None, draw(0), h0d if self.pos_only else None, 0.0, 0.0, 1.0, za, stream)
+            t_table = torch.arange(timesteps + 1, device=dev, dtype=torch.float32) / timesteps
+            ptab = self._prior_table(timesteps, dev) if self.prior_std is not None else None
+            out_samples = [None] * return_frames
+            call = 1
+            use_graph = ((n_samples <= 8 and return_frames == 1 and not torch.cuda.is_current_stream_capturing())
+                         if graph is None else bool(graph))
+            if use_graph:
+                assert return_frames == 1, "intermediate frames need the eager loop"
+                za = self._graphed_steps(dyn, topo, timesteps, za, draw, h0d, edge_index, conditions, n_frag_switch,
+                                         combined_mask, dev, step_callback)
+                call = timesteps + 1
+            for s in (reversed(range(timesteps)) if not use_graph else ()):
+                co = self.schedule.step(s, timesteps)
+                eps_hat, _ = dyn(za, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
                 if ptab is not None:
-                    self._add_prior(eps_hat, za, ptab[0:1])
-                self._step_kernel(topo, 1, za, eps_hat, draw(call), None, fc.inv_alpha_0, fc.sigma_0, fc.sigma_x, zb, stream)
-                x = zb
-                self.last_x = x
-                self.last_status = dyn.last_status
-        finally:
-            dyn.nan_check = old_nan
-        self._check_nan(dyn)
-        nv, nb, pd = self.norm_values, self.norm_biases, self.pos_dim
-        pos = [x[k][:, :pd] * nv[0] + nb[0] for k in range(n_obj)]                              # :680-683
-        if self.pos_only:
-            cat = [h[:, :-1] for h in h0d]                                                      # :542-544
-            charge = [h[:, -1:] for h in h0d]
-        else:
-            cat = [torch.nn.functional.one_hot(torch.argmax(x[k][:, pd:-1] * nv[1] + nb[1], dim=1),
-                                               self.node_nfs[k] - 4).long() for k in range(n_obj)]
-            charge = [torch.round(x[k][:, -1:] * nv[2] + nb[2]).long() for k in range(n_obj)]
-        out_samples[0] = [torch.cat([pos[k], cat[k], charge[k]], dim=1) for k in range(n_obj)]  # :554-557
+                    self._add_prior(eps_hat, za, ptab[s + 1: s + 2])
+                self._step_kernel(topo, 0, za, eps_hat, draw(call), h0d if self.pos_only else None,
+                                  co.alpha_ts, co.c_eps, co.sigma, zb, stream)
+                if step_callback is not None:
+                    step_callback(call)
+                call += 1
+                za, zb = zb, za
+                if (s * return_frames) % timesteps == 0 and return_frames > 1:
+                    out_samples[(s * return_frames) // timesteps] = self._unnormalize_z([z.clone() for z in za])
+            fc = self.schedule.final()
+            eps_hat, _ = dyn(za, edge_index, t_table[0:1], conditions, n_frag_switch, combined_mask)
+            if ptab is not None:
+                self._add_prior(eps_hat, za, ptab[0:1])
+            self._step_kernel(topo, 1, za, eps_hat, draw(call), None, fc.inv_alpha_0, fc.sigma_0, fc.sigma_x, zb, stream)
+            x = zb
+            self.last_x = x
+            self.last_status = dyn.last_status
+        out_samples[0] = self._to_samples(x, h0d, h0_long=False)
         return out_samples, masks
 
     @torch.no_grad()
@@ -364,90 +380,62 @@ class DiffusionSampler:
         assert xh_fixed is not None and len(xh_fixed)
         frag_fixed = list(frag_fixed or [])
         dyn = self.dynamics
-        dev = next(dyn.parameters()).device
-        if dev.type != "cuda":
-            raise _capi.OardError("DiffusionSampler needs the dynamics on a ROCm device (no CPU fallback)")
         n_obj = len(self.node_nfs)
-        masks, combined_mask, edge_index, n_frag_switch = self._layout(fragments_nodes, dev)
-        if conditions is None:
-            conditions = torch.zeros(n_samples, max(dyn.condition_nf, 1), device=dev)
-        conditions = conditions.to(dev)
         pd = self.pos_dim
-        xf = [x.to(device=dev, dtype=torch.float32).clone() for x in xh_fixed]
-        h0 = [x[:, pd:].long().to(torch.float32).contiguous() for x in xf]                 # :753
-        for k in range(n_obj):                                                              # :755-759
-            xf[k][:, :pd] = EGNNDynamics.remove_mean_batch(xf[k][:, :pd], masks[k])
-        sizes = [int(m.numel()) for m in masks]
-        old_nan = dyn.nan_check
-        dyn.nan_check = "replace" if self.on_nan == "replace" else "async"
-        dyn.reset_nan_seen()
-        try:
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                cfg = dyn._config()
-                topo = dyn._get_topology(cfg, edge_index, n_frag_switch, combined_mask, stream)
-                if topo.handle is None:
-                    raise _capi.OardError("the sampling loops run on the production kernels: hidden_channels / num_radial must be a built width "
-                                          "pair (OARD_DIMS=... python -m oareactdiff_amd.build) and a (sample, object) group at most 1024 atoms")
-                counter = [0]
+        with self._run(n_samples, fragments_nodes, conditions) as (dev, layout, conditions, topo, stream):
+            masks, combined_mask, edge_index, n_frag_switch = layout
+            xf = [x.to(device=dev, dtype=torch.float32).clone() for x in xh_fixed]
+            h0 = [x[:, pd:].long().to(torch.float32).contiguous() for x in xf]                 # :753
+            for k in range(n_obj):                                                              # :755-759
+                xf[k][:, :pd] = EGNNDynamics.remove_mean_batch(xf[k][:, :pd], masks[k])
+            sizes = [int(m.numel()) for m in masks]
+            counter = [0]
 
-                def draw():
-                    i = counter[0]
-                    counter[0] += 1
-                    if noise_fn is not None:
-                        return [x.to(device=dev, dtype=torch.float32).contiguous() for x in noise_fn(i)]
-                    return [torch.randn(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
+            def draw():
+                i = counter[0]
+                counter[0] += 1
+                if noise_fn is not None:
+                    return [x.to(device=dev, dtype=torch.float32).contiguous() for x in noise_fn(i)]
+                return [torch.randn(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
 
-                new = lambda: [torch.empty(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
-                hsel = h0 if self.pos_only else None
-                zt = new()
-                self._step_kernel(topo, 2, None, None, draw(), hsel, 0.0, 0.0, 1.0, zt, stream)
-                t_table = torch.arange(timesteps + 1, device=dev, dtype=torch.float32) / timesteps
-                ptab = self._prior_table(timesteps, dev) if self.prior_std is not None else None
-                schedule = get_repaint_schedule(resamplings, jump_length, timesteps)
-                s = timesteps - 1
-                for i, n_denoise in enumerate(schedule):
-                    for j in range(n_denoise):
-                        a_s, sig_s = self.schedule.alpha_sigma(s, timesteps)
-                        known = new()
-                        self._step_kernel(topo, 3, xf, None, draw(), hsel, a_s, 0.0, sig_s, known, stream)   # :797-805
-                        co = self.schedule.step(s, timesteps)
-                        eps_hat, _ = dyn(zt, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
-                        if ptab is not None:
-                            self._add_prior(eps_hat, zt, ptab[s + 1: s + 2])
-                        unknown = new()
-                        self._step_kernel(topo, 0, zt, eps_hat, draw(), hsel, co.alpha_ts, co.c_eps, co.sigma, unknown, stream)
-                        zt = [known[k] if k in frag_fixed else unknown[k] for k in range(n_obj)]            # :827-830
-                        if j == n_denoise - 1 and i < len(schedule) - 1:                                   # :833-850
-                            t = s + jump_length
-                            a_ts, sig_ts = self.schedule.forward_jump(s, t, timesteps)
-                            jumped = new()
-                            self._step_kernel(topo, 4, zt, None, draw(), None, a_ts, 0.0, sig_ts, jumped, stream)
-                            zt = jumped
-                            s = t
-                        s -= 1
-                fc = self.schedule.final()
-                eps_hat, _ = dyn(zt, edge_index, t_table[0:1], conditions, n_frag_switch, combined_mask)
-                if ptab is not None:
-                    self._add_prior(eps_hat, zt, ptab[0:1])
-                x = new()
-                self._step_kernel(topo, 1, zt, eps_hat, draw(), None, fc.inv_alpha_0, fc.sigma_0, fc.sigma_x, x, stream)
-                self.last_x = x
-                self.last_status = dyn.last_status
-        finally:
-            dyn.nan_check = old_nan
-        self._check_nan(dyn)
-        nv, nb = self.norm_values, self.norm_biases
-        pos = [x[k][:, :pd] * nv[0] + nb[0] for k in range(n_obj)]
-        if self.pos_only:
-            cat = [h[:, :-1].long() for h in h0]
-            charge = [h[:, -1:].long() for h in h0]
-        else:
-            cat = [torch.nn.functional.one_hot(torch.argmax(x[k][:, pd:-1] * nv[1] + nb[1], dim=1),
-                                               self.node_nfs[k] - 4).long() for k in range(n_obj)]
-            charge = [torch.round(x[k][:, -1:] * nv[2] + nb[2]).long() for k in range(n_obj)]
+            new = lambda: [torch.empty(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
+            hsel = h0 if self.pos_only else None
+            zt = new()
+            self._step_kernel(topo, 2, None, None, draw(), hsel, 0.0, 0.0, 1.0, zt, stream)
+            t_table = torch.arange(timesteps + 1, device=dev, dtype=torch.float32) / timesteps
+            ptab = self._prior_table(timesteps, dev) if self.prior_std is not None else None
+            schedule = get_repaint_schedule(resamplings, jump_length, timesteps)
+            s = timesteps - 1
+            for i, n_denoise in enumerate(schedule):
+                for j in range(n_denoise):
+                    a_s, sig_s = self.schedule.alpha_sigma(s, timesteps)
+                    known = new()
+                    self._step_kernel(topo, 3, xf, None, draw(), hsel, a_s, 0.0, sig_s, known, stream)   # :797-805
+                    co = self.schedule.step(s, timesteps)
+                    eps_hat, _ = dyn(zt, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
+                    if ptab is not None:
+                        self._add_prior(eps_hat, zt, ptab[s + 1: s + 2])
+                    unknown = new()
+                    self._step_kernel(topo, 0, zt, eps_hat, draw(), hsel, co.alpha_ts, co.c_eps, co.sigma, unknown, stream)
+                    zt = [known[k] if k in frag_fixed else unknown[k] for k in range(n_obj)]            # :827-830
+                    if j == n_denoise - 1 and i < len(schedule) - 1:                                   # :833-850
+                        t = s + jump_length
+                        a_ts, sig_ts = self.schedule.forward_jump(s, t, timesteps)
+                        jumped = new()
+                        self._step_kernel(topo, 4, zt, None, draw(), None, a_ts, 0.0, sig_ts, jumped, stream)
+                        zt = jumped
+                        s = t
+                    s -= 1
+            fc = self.schedule.final()
+            eps_hat, _ = dyn(zt, edge_index, t_table[0:1], conditions, n_frag_switch, combined_mask)
+            if ptab is not None:
+                self._add_prior(eps_hat, zt, ptab[0:1])
+            x = new()
+            self._step_kernel(topo, 1, zt, eps_hat, draw(), None, fc.inv_alpha_0, fc.sigma_0, fc.sigma_x, x, stream)
+            self.last_x = x
+            self.last_status = dyn.last_status
         out_samples = [None] * return_frames
-        out_samples[0] = [torch.cat([pos[k], cat[k], charge[k]], dim=1) for k in range(n_obj)]
+        out_samples[0] = self._to_samples(x, h0, h0_long=True)
         return out_samples, masks
 
     def _unnormalize_z(self, z: List[Tensor]) -> List[Tensor]:

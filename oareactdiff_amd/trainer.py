@@ -21,7 +21,7 @@ left out of the bucket and never get a gradient, as in the reference.
 from __future__ import annotations
 
 import copy
-import contextlib
+import ctypes as C
 import math
 import os
 from collections.abc import Mapping
@@ -32,6 +32,8 @@ import torch
 import torch.distributed as dist
 from torch import Tensor, nn
 
+from . import _capi, training
+from .dynamics import _CallBuffers
 from .loss import DiffusionLoss
 
 UNUSED_PREFIXES = ("model.distance_embedding.", "model.last_layer.")
@@ -116,7 +118,7 @@ class DDPMTrainer:
         if int(microbatches) not in (1, 2):
             raise ValueError("microbatches must be 1 or 2")
         self.microbatches = int(microbatches)
-        self._mb = None                                # second micro-batch: stream, gradient buffer, the module's per-call buffers
+        self._mb = None                                # second micro-batch: stream, gradient buffer, its own per-call buffers
         self._clip_state = None                        # device mirror of (history, opt_step, skipped_steps) while host_sync is off
         self.loss = DiffusionLoss(dynamics, noise_schedule, timesteps, precision, norm_values=norm_values,
                                   norm_biases=norm_biases, pos_only=pos_only, fixed_idx=fixed_idx, loss_type=loss_type,
@@ -337,12 +339,11 @@ class DDPMTrainer:
 
     # ---- fused step (HIP module): no autograd graph, ~20 launches around the network call ----------------------------------------
     def _fused_part(self, cfg, packed, reps, cond, t_int: Tensor, noise: List[Tensor], counts: List[int], host_masks, host_sizes,
-                    terms: Tensor, col0: int):
+                    terms: Tensor, col0: int, buffers: Optional[_CallBuffers] = None):
         """One (micro-)batch on the CURRENT stream: oard_loss_prepare -> oard_forward_train -> oard_loss_terms.  `terms` [2K, B_total]: the
         step's logged terms; this part owns columns [col0, col0 + B) (oard_loss_terms takes B_total both as the row stride of `terms` and
-        as the 1 / B of the mean nll).  -> (nll [B], d(mean nll)/d(net), TrainState)."""
-        import ctypes as C
-        from . import _capi
+        as the 1 / B of the mean nll).  `buffers`: the per-call buffers of the network call (None: the module's own).
+        -> (nll [B], d(mean nll)/d(net), TrainState)."""
         dyn, ls = self.dynamics, self.loss
         dev = self.flat_grad.device
         K = len(reps)
@@ -363,7 +364,7 @@ class DDPMTrainer:
         charge = [r["charge"].detach().to(torch.int64).contiguous() for r in reps]
         z = [torch.empty(counts[k], nfs[k], device=dev) for k in range(K)]
         eps = [torch.empty_like(x) for x in z]
-        arr = lambda ts: (C.c_void_p * K)(*[t.data_ptr() for t in ts])      # noqa: E731
+        arr = _capi.ptr_array
         f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])              # noqa: E731
         nv, nb = f3(ls.norm_values), f3(ls.norm_biases)
         sc = (C.c_float * K)(*[float(x) for x in ls.scales[:K]])
@@ -372,8 +373,8 @@ class DDPMTrainer:
                                         gamma.data_ptr(), ls.T, nv, nb, 1 if ls.pos_only else 0, fixed_mask, arr(z), arr(eps), stream),
                     "oard_loss_prepare")
         t = (t_int / ls.T).view(B, 1)
-        xs, tt, t_scalar, cnd = dyn._train_inputs(topo, z, t, cond, dev)
-        net, state = dyn._run_forward_train(cfg, topo, packed, xs, tt, t_scalar, cnd, stream, reuse_tape=True)
+        xs, tt, t_scalar, cnd = dyn._inputs(topo, z, t, cond, dev, detach=True)
+        net, state = dyn._run_forward_train(cfg, topo, packed, xs, tt, t_scalar, cnd, stream, reuse_tape=True, buffers=buffers)
         nll = torch.empty(B, device=dev)
         dnet = [torch.empty_like(o) for o in net]
         B_total = int(terms.shape[1])
@@ -385,10 +386,9 @@ class DDPMTrainer:
 
     def _second_slot(self, dev):
         """State of the second micro-batch: the library's idle sub-batch stream (no fifth stream in the process: the runtime serves a
-        process's streams from 4 hardware queues), a gradient buffer with the bucket's layout, and the module's per-call buffers."""
+        process's streams from 4 hardware queues), a gradient buffer with the bucket's layout, and per-call buffers of its own (workspace,
+        tape, sweep scratch, NaN flag: the module's set serves the first half)."""
         if self._mb is None or self._mb["device"] != dev:
-            import ctypes as C
-            from . import _capi
             h = C.c_void_p()
             with torch.cuda.device(dev):
                 _capi.check(_capi.lib().oard_library_stream(1, C.byref(h)), "oard_library_stream")
@@ -397,34 +397,15 @@ class DDPMTrainer:
             for p in self.params:
                 dests2[id(p)] = grad2[off: off + p.numel()].view_as(p)
                 off += p.numel()
-            self._mb = {"device": dev, "stream": torch.cuda.ExternalStream(h.value, device=dev), "grad": grad2, "dests": dests2, "buffers": {}}
+            self._mb = {"device": dev, "stream": torch.cuda.ExternalStream(h.value, device=dev), "grad": grad2, "dests": dests2,
+                        "buffers": _CallBuffers()}
         return self._mb
-
-    @contextlib.contextmanager
-    def _slot(self, i: int):
-        """The module's per-call buffers (workspace, tape, sweep scratch, NaN flag) of micro-batch i: the second one has its own."""
-        if i == 0:
-            yield
-            return
-        dyn, names = self.dynamics, ("_ws", "_tape_buf", "_train_scratch", "nan_seen")
-        saved = {n: getattr(dyn, n, None) for n in names}
-        store = self._mb["buffers"]
-        for n in names:
-            setattr(dyn, n, store.get(n))
-        try:
-            yield
-        finally:
-            for n in names:
-                store[n] = getattr(dyn, n, None)
-                setattr(dyn, n, saved[n])
 
     def _fused_forward_backward(self, batch, t_int: Optional[Tensor] = None, draw=None):
         """loss terms + gradients into the bucket: oard_loss_prepare -> oard_forward_train -> oard_loss_terms -> the backward sweep
         (training.Sweep) fed with the closed-form d(mean nll)/d(net).  Returns (nll [B], terms [2K, B]) on the device.
         Injected draws (`draw`) follow DiffusionLoss's protocol (per object: randn(n, 3) then randn(n, nf - 3)); the default is ONE
         device randn for the whole step's noise (same distribution, one launch instead of nine)."""
-        import ctypes as C
-        from . import _capi, training
         reps, cond = batch
         dyn, ls = self.dynamics, self.loss
         dev = self.flat_grad.device
@@ -463,11 +444,10 @@ class DDPMTrainer:
 
     def _fused_two(self, cfg, packed, reps, cond, t_int, noise, B: int, dests, main, terms):
         """The step as two micro-batches (reactions [0, h) and [h, B)) on two streams; see `microbatches` in __init__."""
-        from . import training
         dyn = self.dynamics
         dev = self.flat_grad.device
         mb = self._second_slot(dev)
-        side = mb["stream"]
+        side, buf1 = mb["stream"], mb["buffers"]
         K = len(reps)
         h = B // 2
         n0 = [int(r["size_host"][:h].sum()) for r in reps]                 # rows of the first half per object (host arithmetic)
@@ -485,31 +465,27 @@ class DDPMTrainer:
             halves.append((rp, cd, t_int[lo:hi], nz, cn, hm, hs, terms, lo))
         dyn._get_packed_bwd(cfg, main.cuda_stream)             # both packs on the caller's stream BEFORE the fork (the second half reads them)
         mb["grad"].zero_()
-        if mb["buffers"].get("nan_seen") is not None:
-            mb["buffers"]["nan_seen"].zero_()
+        buf1.reset()
         side.wait_stream(main)
-        with torch.cuda.stream(side), self._slot(1):
-            nll1, dnet1, st1 = self._fused_part(cfg, packed, *halves[1])
+        with torch.cuda.stream(side):
+            nll1, dnet1, st1 = self._fused_part(cfg, packed, *halves[1], buffers=buf1)
         nll0, dnet0, st0 = self._fused_part(cfg, packed, *halves[0])
-        with torch.cuda.stream(side), self._slot(1):
-            sw1 = training.Sweep(dyn, st1, dnet1, side.cuda_stream, mb["dests"])
+        with torch.cuda.stream(side):
+            sw1 = training.Sweep(dyn, st1, dnet1, side.cuda_stream, mb["dests"], buf1)
         sw0 = training.Sweep(dyn, st0, dnet0, main.cuda_stream, dests)
         # the two sweeps step by step: the library's gradient stream then sees their weight-gradient work alternately
         steps = [("tail",)] + [("layer", l) for l in reversed(range(sw0.NL))] + [("init",)]
         for st in steps:
-            with torch.cuda.stream(side), self._slot(1):
+            with torch.cuda.stream(side):
                 getattr(sw1, st[0])(*st[1:])
             getattr(sw0, st[0])(*st[1:])
         main.wait_stream(side)
         self.flat_grad.add_(mb["grad"])
-        seen1 = mb["buffers"].get("nan_seen")
-        if seen1 is not None and dyn.nan_seen is not None:
-            dyn.nan_seen.bitwise_or_(seen1)
+        if buf1.nan_seen is not None and dyn.nan_seen is not None:
+            dyn.nan_seen.bitwise_or_(buf1.nan_seen)       # the second half's flag reaches the module's, which the step reads
         return torch.cat([nll0, nll1]), terms
 
     def _fused_step(self, batch, **kw) -> Dict[str, float]:
-        import ctypes as C  # noqa: F401
-        from . import _capi
         dyn = self.dynamics
         prev = dyn.nan_check
         dyn.nan_check = "async"
@@ -544,7 +520,7 @@ class DDPMTrainer:
                     float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), 1 if o.get("amsgrad", False) else 0,
                     1 if self.clip_grad else 0, state.data_ptr(), self.CLIP_CAPACITY, stats_dev.data_ptr(),
                     stats_dev.data_ptr() + 4, out4.data_ptr(), stream), "oard_adamw_step_dev")
-            dyn._packed_key = dyn._packed_bwd_key = None      # the weights changed (unless the step was skipped: repacking is harmless)
+            dyn.invalidate_packed()                   # the weights changed (unless the step was skipped: repacking is harmless)
             return LazyInfo(stats_dev, out4, K, [float(x) for x in self.loss.scales], self.clip_grad)
         if self._clip_state is not None:               # host_sync was switched on again: the host copies become the truth
             self._pull_clip_state()
@@ -582,7 +558,7 @@ class DDPMTrainer:
                                                         float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]), float(o.get("eps", 1e-8)),
                                                         float(o.get("weight_decay", 0.0)), self.opt_step, 1 if o.get("amsgrad", False) else 0,
                                                         float(gscale), stream), "oard_adamw_step")
-            dyn._packed_key = dyn._packed_bwd_key = None      # the weights changed behind torch's version counters
+            dyn.invalidate_packed()                   # the weights changed behind torch's version counters
         info["loss"] = stats[2]
         info["skipped"] = int(skipped)
         return info

@@ -61,6 +61,7 @@ class TrainTopology:
                                                  C.cast(nfs.data_ptr(), C.POINTER(C.c_int64)), cm.numel(), 1, C.byref(h)),
                     "oard_topology_create_parts")
         self.handle, self._lib = h, L
+        self.key_tensors = None                        # set by the cache that holds this topology (dynamics._TensorKeyCache)
         self.N, self.E = int(L.oard_topology_num_nodes(h)), int(L.oard_topology_num_edges(h))
         self.A, self.B = int(L.oard_topology_num_inner_edges(h)), int(L.oard_topology_num_samples(h))
         self.n_obj = cfg.n_obj
@@ -129,6 +130,7 @@ class TrainState:
                  cond: Optional[Tensor]):
         self.cfg, self.topo, self.tape = cfg, topo, tape
         self.xh, self.t, self.t_scalar, self.cond = xh, t, t_scalar, cond
+        self.keep_inputs = self.keepalive = None       # what the asynchronous launches of the step / of the sweep still read
 
 
 def _wgrad(dY: Tensor, ncY: int, o_len: int, o_pad: int, MO: int, X: Tensor, ncX: int, x_silu: bool, i_len: int,
@@ -192,13 +194,8 @@ def gradient_table(dyn, dests: Dict[int, Tensor]):
     """(void* array in the canonical parameter order of oard_pack_weights) for the gradient destinations: `dests` maps id(param) ->
     contiguous float32 tensor of the parameter's shape; parameters without an entry, buffers and the two modules the forward
     never uses get NULL (the sweep skips them)."""
-    tensors = dyn._ordered_tensors()
-    names = list(dyn._spec)
-    ptrs = []
-    for name, t in zip(names, tensors):
-        d = dests.get(id(t)) if isinstance(t, nn.Parameter) and not name.startswith(UNUSED_PREFIXES) else None
-        ptrs.append(d.data_ptr() if d is not None else None)
-    return (C.c_void_p * len(ptrs))(*ptrs)
+    return _capi.ptr_array([dests.get(id(t)) if isinstance(t, nn.Parameter) and not name.startswith(UNUSED_PREFIXES) else None
+                            for name, t in zip(dyn._spec, dyn._ordered_tensors())])
 
 
 class Sweep:
@@ -208,10 +205,11 @@ class Sweep:
     as a whole would park the other's weight gradients - and with them its cotangent chain, which waits for the scratch buffers they
     read - behind all of its own).
     `dests` (id(param) -> tensor): accumulate INTO these tensors (e.g. the `.grad` views of a flat bucket); None: accumulate into a fresh
-    zero-filled flat buffer, `self.out` = {canonical name: view}.  `scratch`: a uint8 buffer of at least oard_train_scratch_bytes, or None
-    (then `dyn._train_scratch`, grown on demand)."""
+    zero-filled flat buffer, `self.out` = {canonical name: view}.  `buffers`: the per-call buffer set whose scratch the sweep uses - the one
+    its forward ran on (None: the module's own)."""
 
-    def __init__(self, dyn, st: TrainState, grad_outs: List[Optional[Tensor]], stream: int, dests: Optional[Dict[int, Tensor]] = None):
+    def __init__(self, dyn, st: TrainState, grad_outs: List[Optional[Tensor]], stream: int, dests: Optional[Dict[int, Tensor]] = None,
+                 buffers=None):
         L = _capi.lib()
         self.L, self.st, self.stream = L, st, stream
         cfg, topo, tape = st.cfg, st.topo, st.tape
@@ -221,11 +219,7 @@ class Sweep:
         dev = st.xh[0].device
         n_obj = len(dyn.node_nfs)
         packed, pbwd = dyn._get_packed(cfg, stream), dyn._get_packed_bwd(cfg, stream)
-        need = L.oard_train_scratch_bytes(C.byref(cfg), topo.handle)
-        sc = getattr(dyn, "_train_scratch", None)
-        if sc is None or sc.numel() < need or sc.device != dev:
-            sc = torch.empty(need, dtype=torch.uint8, device=dev)
-            dyn._train_scratch = sc
+        sc = (dyn._call_buffers if buffers is None else buffers).scratch(L.oard_train_scratch_bytes(C.byref(cfg), topo.handle), dev)
         self.out: Dict[str, Tensor] = {}
         if dests is None:
             names = dyn._param_names()
@@ -239,14 +233,13 @@ class Sweep:
                 dests[id(p)] = self.out[n]
                 off += p.numel()
         tensors = dyn._ordered_tensors()
-        self.params = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        self.params = _capi.ptr_array(tensors)
         self.grads = gradient_table(dyn, dests)
         gos = []
         for k in range(n_obj):
             g = grad_outs[k] if k < len(grad_outs) else None
             gos.append(None if g is None else g.to(torch.float32).contiguous())
-        self.go = (C.c_void_p * n_obj)(*[g.data_ptr() if g is not None else None for g in gos])
-        self.xhp = (C.c_void_p * n_obj)(*[x.data_ptr() for x in st.xh])
+        self.go, self.xhp = _capi.ptr_array(gos), _capi.ptr_array(st.xh)
         ds = torch.empty(N, HP, device=dev)
         dvec = torch.empty(3 * N, HP, device=dev)
         # cotangent of the edge state, updated in place layer by layer.  Nothing flows into the FINAL edge state: the last layer's kernels
@@ -275,13 +268,13 @@ class Sweep:
 
 
 def backward_sweep(dyn, st: TrainState, grad_outs: List[Optional[Tensor]], stream: int,
-                   dests: Optional[Dict[int, Tensor]] = None) -> Dict[str, Tensor]:
+                   dests: Optional[Dict[int, Tensor]] = None, buffers=None) -> Dict[str, Tensor]:
     """d(loss)/d(parameter) for every parameter the forward uses, given d(loss)/d(out[k]).
     `dests` (id(param) -> tensor): accumulate INTO these tensors (e.g. the `.grad` views of a flat bucket) and return {};
-    None: accumulate into a fresh zero-filled flat buffer and return {canonical name: view}."""
+    None: accumulate into a fresh zero-filled flat buffer and return {canonical name: view}.  `buffers`: as for `Sweep`."""
     tm = _StageTimer()
     tm.mark("start")
-    sw = Sweep(dyn, st, grad_outs, stream, dests)
+    sw = Sweep(dyn, st, grad_outs, stream, dests, buffers)
     sw.tail()
     tm.mark("tail")
     for l in reversed(range(sw.NL)):
@@ -314,7 +307,7 @@ class DynamicsFunction(torch.autograd.Function):
         dev = st.xh[0].device
         P = dyn._param_dict()
         dests = None
-        if getattr(dyn, "grad_inplace", False):
+        if dyn.grad_inplace:
             dests = {}
             for n in ctx.names:
                 p = P[n]

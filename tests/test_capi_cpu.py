@@ -121,3 +121,58 @@ def test_checkpoint_adapter_round_trip():
     assert set(extract_dynamics_state({"dynamics." + k: v for k, v in sd.items()})) == set(sd)
     with pytest.raises(KeyError):
         extract_dynamics_state({"foo.bar": torch.zeros(1)})
+
+
+def test_call_buffers_grow_only_and_keep_the_sticky_flag():
+    """`dynamics._CallBuffers`, the one owner of what a network call scribbles on, on the host (it only allocates and ORs): a buffer is
+    reused while it is large enough and replaced when it is not, the tape is a view of exactly the requested bytes over ONE buffer
+    with 1/8 headroom, the NaN flag accumulates with OR and is cleared in place."""
+    from oareactdiff_amd.dynamics import EGNNDynamics, _CallBuffers
+    cpu = torch.device("cpu")
+    b = _CallBuffers()
+    assert b.ws is None and b.tape_buf is None and b.scratch_buf is None and b.nan_seen is None
+    b.reset()                                                   # nothing to clear yet
+    w = b.workspace(100, cpu)
+    assert w.dtype == torch.uint8 and w.numel() >= 100
+    assert b.workspace(50, cpu) is w and b.ws is w
+    w2 = b.workspace(200, cpu)
+    assert w2 is not w and w2.numel() >= 200 and b.ws is w2
+    s = b.scratch(64, cpu)
+    assert b.scratch(64, cpu) is s and b.scratch(65, cpu) is not s and b.scratch_buf.numel() >= 65
+    n = 1000
+    t = b.tape(n, cpu)
+    assert t.numel() == n and b.tape_buf.numel() >= n + n // 8 and t.data_ptr() == b.tape_buf.data_ptr()
+    buf = b.tape_buf
+    t2 = b.tape(400, cpu)
+    assert b.tape_buf is buf and t2.numel() == 400 and t2.data_ptr() == buf.data_ptr()
+    assert b.tape(n + n // 8 + 1, cpu).numel() == n + n // 8 + 1 and b.tape_buf is not buf
+    b.note(torch.tensor([1, 0], dtype=torch.int32))
+    flag = b.nan_seen
+    b.note(torch.tensor([0, 4], dtype=torch.int32))
+    b.note(torch.tensor([2, 0], dtype=torch.int32))
+    assert b.nan_seen is flag and flag.tolist() == [3, 4]
+    ptr = flag.data_ptr()
+    b.reset()
+    assert b.nan_seen is flag and flag.data_ptr() == ptr and flag.tolist() == [0, 0]
+    # the module's `_ws` / `nan_seen` are views onto its own set, readable and writable
+    c = Case("g1_wrapper_small")
+    d = EGNNDynamics(model_config=dict(c.cfg), fragment_names=["a", "b", "c"], node_nfs=c.node_nfs, edge_nf=0, condition_nf=c.cnf, device=cpu)
+    assert d._ws is None and d.nan_seen is None
+    d.reset_nan_seen()
+    d.nan_seen = torch.tensor([5, 0], dtype=torch.int32)
+    d._ws = w2
+    assert d._call_buffers.nan_seen is d.nan_seen and d._call_buffers.ws is w2 and d._ws is w2
+    d.reset_nan_seen()
+    assert d.nan_seen.tolist() == [0, 0]
+
+
+def test_ptr_array_maps_none_to_null():
+    from oareactdiff_amd import _capi
+    assert _capi.ptr_array(None) is None
+    a, b = torch.zeros(3), torch.zeros(2, 2)
+    arr = _capi.ptr_array([a, None, b])
+    assert isinstance(arr, C.Array) and arr._type_ is C.c_void_p and len(arr) == 3
+    assert arr[0] == a.data_ptr() and arr[1] is None and arr[2] == b.data_ptr()
+    padded = _capi.ptr_array([a], 4)
+    assert len(padded) == 4 and padded[0] == a.data_ptr() and padded[1] is None and padded[3] is None
+    assert len(_capi.ptr_array([], 2)) == 2 and len(_capi.ptr_array([])) == 0

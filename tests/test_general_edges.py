@@ -225,3 +225,28 @@ def test_arbitrary_edge_lists_are_taken_as_given(seed):
     print(f"random graph {seed}: vel {rel(v, rv):.2e} h {rel(h, rh):.2e}")
     assert rel(v, rv) <= TOL and rel(h, rh) <= TOL
 
+
+@pytest.mark.parametrize("name", ["g11_arbitrary", "g2_prod_b2_n23"])
+def test_forced_general_path_builds_no_production_tables(name):
+    """`edge_list_path = "general"` on a list that is not the complete graph (g11_arbitrary) and on one that is (g2_prod_b2_n23): the
+    topology holds a general graph and no production handle, nothing warns (the "outside the production tables" warning is for
+    calls that were NOT forced), and the outputs are those of the unforced module bit for bit where that one runs the general path
+    too, and within the fixture's gate of the float64 reference where it would have run the production kernels."""
+    import warnings
+    dev = torch.device("cuda:0")
+    c = Case(name)
+    with warnings.catch_warnings(record=True) as caught, torch.no_grad():
+        warnings.simplefilter("always")
+        g = _dyn(c, dev, "general")
+        b, _ = g(*_args(c, dev))
+    assert not caught, [str(w.message) for w in caught]
+    assert g._last_topo.handle is None and g._last_topo.graph is not None
+    if name == "g11_arbitrary":
+        with torch.no_grad():
+            a, _ = _dyn(c, dev)(*_args(c, dev))
+        assert all(torch.equal(x, y) for x, y in zip(a, b))
+    else:
+        v, h = c.split([o.cpu() for o in b])
+        rv, rh = c.split(c.ref64)
+        print(f"{name} forced general: vel {rel(v, rv):.2e} h {rel(h, rh):.2e}")
+        assert rel(v, rv) <= TOL and rel(h, rh) <= TOL

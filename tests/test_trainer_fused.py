@@ -379,3 +379,64 @@ def test_two_microbatches_give_the_step_of_one(name, pos_only):
         torch.cuda.synchronize()
         w[mb] = tr.flat_param.clone()
     assert float((w[1] - w[2]).abs().max()) <= 1e-6 * float(w[1].abs().max())
+
+
+def _two_halves_setup(dev):
+    """g9_grad_prod_l2 with its recorded time steps and draws, a two-micro-batch trainer and a maker of host-carrying batches."""
+    from oareactdiff_amd.trainer import DDPMTrainer
+    c = GradCase("g9_grad_prod_l2")
+    B = len(c.meta["sizes"])
+    assert B >= 2
+    t_int = torch.tensor(c.meta["t_int"], dtype=torch.float32, device=dev).view(-1, 1)
+
+    def draws():
+        it = iter(range(c.meta["n_randn"]))
+        return lambda shape: torch.from_numpy(c.z[f"randn{next(it)}"]).to(dev)
+
+    def batch(nan_in_last_row=False):
+        reps = c.reps(torch.float32, "cpu")
+        if nan_in_last_row:                                    # last row of the last object: a reaction of the second half
+            assert int(reps[-1]["mask"][-1]) >= B // 2
+            reps[-1]["pos"] = reps[-1]["pos"].clone()
+            reps[-1]["pos"][-1, 0] = float("nan")
+        return DDPMTrainer.to_device((reps, torch.zeros(B, 1)), dev, non_blocking=False)
+    return _trainer(c, dev, True, False, microbatches=2), t_int, draws, batch
+
+
+def test_second_halfs_nan_flag_reaches_the_module():
+    """The second micro-batch notes its calls' NaN status in a flag of its own; the step reads the module's: a NaN that only a
+    reaction of the second half sees must arrive there, and a clean step after a reset must leave it clear."""
+    dev = torch.device("cuda:0")
+    tr, t_int, draws, batch = _two_halves_setup(dev)
+    dyn = tr.dynamics
+    dyn.nan_check = "async"
+    for poisoned in (True, False):
+        dyn.reset_nan_seen()
+        tr._bucket.zero_()
+        tr._fused_forward_backward(batch(poisoned), t_int=t_int, draw=draws())
+        torch.cuda.synchronize()
+        assert tr._mb is not None                              # the two-micro-batch step ran
+        assert (int(dyn.nan_seen[0]) != 0) == poisoned
+
+
+def test_second_half_owns_its_buffers_and_the_modules_survive():
+    """After a two-micro-batch step the module's workspace is the tensor a one-batch forward of the same size left there (the halves
+    need less, and the second one never touches it), and the second half's workspace, tape and sweep scratch exist and are not the
+    module's."""
+    dev = torch.device("cuda:0")
+    tr, t_int, draws, batch = _two_halves_setup(dev)
+    dyn = tr.dynamics
+    tr.microbatches = 1
+    tr._bucket.zero_()
+    tr._fused_forward_backward(batch(), t_int=t_int, draw=draws())
+    ws = dyn._ws
+    assert ws is not None and tr._mb is None
+    ptr = ws.data_ptr()
+    tr.microbatches = 2
+    tr.training_step(batch(), t_int=t_int, draw=draws())
+    torch.cuda.synchronize()
+    assert dyn._ws is ws and ws.data_ptr() == ptr
+    own, second = dyn._call_buffers, tr._mb["buffers"]
+    for name in ("ws", "tape_buf", "scratch_buf"):
+        a, b = getattr(own, name), getattr(second, name)
+        assert a is not None and b is not None and a.data_ptr() != b.data_ptr(), name

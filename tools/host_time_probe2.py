@@ -16,7 +16,7 @@ dev = torch.device("cuda:0")
 dyn = bench.new_dynamics(dev)
 tr = DDPMTrainer(dyn, timesteps=1000, norm_values=(1.0, 4.0, 10.0), scales=(1.0, 2.0, 1.0), pos_only=True, host_sync=False)
 for o, n in ((loss.DiffusionLoss, "_layout"), (dynamics.EGNNDynamics, "_get_train_topology"), (dynamics.EGNNDynamics, "_get_packed"),
-             (dynamics.EGNNDynamics, "_get_packed_bwd"), (dynamics.EGNNDynamics, "_train_inputs"), (dynamics.EGNNDynamics, "_run_forward_train"),
+             (dynamics.EGNNDynamics, "_get_packed_bwd"), (dynamics.EGNNDynamics, "_inputs"), (dynamics.EGNNDynamics, "_run_forward_train"),
              (dynamics.EGNNDynamics, "_ordered_tensors"), (training, "backward_sweep"), (training, "gradient_table"),
              (training.TrainTopology, "__init__", ), (DDPMTrainer, "_fused_forward_backward"), (DDPMTrainer, "_fused_step")):
     wrap(o, n, f"{o.__name__}.{n}")
