@@ -22,7 +22,9 @@
 #include "oard_edge_v1.h"
 
 // TRAIN: as k_gcl_edge_v1's training mode - the new state goes to a different buffer, the pre-activations z1 / z2 / att / z3 are taped.
-template <class D, bool DO_S1, bool DO_S3, bool TRAIN = false>
+// MSUM: as k_gcl_edge_v1's - the launch walks the source-major column list, `mbuf` is msum (per-node partial sums, st_msum).  The wave
+// tiles stay on absolute multiples of 16 columns (r0 is one), so a node's partial sums are those of the tile kernel bit for bit.
+template <class D, bool DO_S1, bool DO_S3, bool TRAIN = false, bool MSUM = false>
 __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* __restrict__ stream,
                                                        const float* __restrict__ P, const float* __restrict__ Q,
                                                        const float* __restrict__ u0, const float* __restrict__ c0,
@@ -36,6 +38,7 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
     constexpr int P0 = DO_S1 ? 0 : S::NP1, PEND = DO_S3 ? S::NPH : S::NP1 + S::NP2, NPR = PEND - P0;     // local phases of a round
     static_assert(NPR >= DIST, "a round must be at least as long as the prefetch distance");
     static_assert(HT >= 2, "the phase barrier sits inside the first chain of a phase");
+    static_assert(!MSUM || !TRAIN, "the training-mode forward tapes agg from the per-edge message rows");
     constexpr int BAR_AT = OARD_BAR_AT < HT / 2 ? OARD_BAR_AT : HT / 2;
 
     const int lane = threadIdx.x & 63, g = lane >> 4;
@@ -53,6 +56,18 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
         const int slot = is_half(r) ? wave - 4 : wave;
         const long long c = r0 + (((hb0 + 2 * r) << 2) + slot) * 16 + (lane & 15);
         return (size_t)((slot >= 0 && c < r1) ? c : tp.E);
+    };
+    // MSUM: the launch walks the source-major column list - this lane's column in round r (stored to by segment heads only: real columns)
+    // and its table entry (row, source, target, segment key) as one 16-byte load; padding columns get the spare row and key -1
+    auto col_of = [&](int r) -> long long {
+        return r0 + (((hb0 + 2 * r) << 2) + (is_half(r) ? wave - 4 : wave)) * 16 + (lane & 15);
+    };
+    auto info_of = [&](int r) -> i4 {
+        const int slot = is_half(r) ? wave - 4 : wave;
+        const long long c = col_of(r);
+        i4 ci = {(int)tp.E, 0, 0, -1};
+        if (slot >= 0 && c < r1) ci = *reinterpret_cast<const i4*>(tp.col_info + 4 * c);
+        return ci;
     };
 
     SlabPrefetch<WAVES, S::SLAB, 1, 1, RING> pf;
@@ -98,9 +113,11 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
     float* orow = nullptr;
     f4 h1[HT];
     f4 xn[GP];
+    // MSUM: padding columns read the state of a real row (see k_gcl_edge_v1: every lane must hold finite values)
+    auto rd_row = [&](size_t row) -> size_t { return (MSUM && row == (size_t)tp.E) ? (size_t)tp.col_info[4 * r0] : row; };
     auto set_rows = [&](size_t row) {
         e = row;
-        erow = ew_in + e * D::WP + 4 * g;
+        erow = ew_in + rd_row(e) * D::WP + 4 * g;
         orow = ew_out + e * D::WP + 4 * g;
     };
     auto load_xn = [&](f4 (&x)[GP], const float* er) {
@@ -108,7 +125,7 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
         for (int gg = 0; gg < GP; ++gg) x[gg] = (DO_S1 && gg < WB) ? ld_edge(er + 16 * gg) : f4zero();
     };
     size_t eid = 0;
-    int src = 0, tgt = 0;
+    int src = 0, tgt = 0, key = 0;                             // key (MSUM): segment key of this round's column (seg_lanes)
     // h1 in front of the round: zero with S1 (P[src] + Q[tgt] are added behind S1, gathers in flight during its last phase),
     // P + Q + u0 without
     auto load_h1 = [&]() {
@@ -119,8 +136,8 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
         }
     };
     if (active_in(0)) {
-        set_rows(row_of(0));
-        eid = (size_t)tp.row_eid[e]; src = tp.row_src[e]; tgt = tp.row_tgt[e];
+        if (MSUM) { const i4 ci = info_of(0); set_rows((size_t)ci.x); src = ci.y; tgt = ci.z; key = ci.w; }
+        else { set_rows(row_of(0)); eid = (size_t)tp.row_eid[e]; src = tp.row_src[e]; tgt = tp.row_tgt[e]; }
         load_h1();
         load_xn(xn, erow);
     }
@@ -141,6 +158,8 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
         // as loop-carried variables they would be live through S1 and S2 as well)
         int src_n = 0, tgt_n = 0;
         size_t eid_n = 0;
+        i4 ci_n = {0, 0, 0, -1};                               // MSUM: the next round's table entry, fetched in the first S3 phase
+        auto next_row = [&]() -> size_t { return (MSUM && DO_S3) ? (size_t)ci_n.x : row_of(r + 1); };
         f4 xn_n[GP];
         f4 hp[HT], hq[HT];                                     // P[src], Q[tgt]: in flight during the last S1 phase
         int lp = P0;                                           // local phase
@@ -258,8 +277,11 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
                 if ((S::NP2 - 1) * GP + gg < HT) st_blk(tape.z2, e, D::HP, (S::NP2 - 1) * GP + gg, lane, pz2[gg]);
         }
         if (!DO_S3) {
+            if (MSUM) st_msum<D>(mbuf, col_of(r), key, m, lane);
+            else {
 #pragma unroll
-            for (int t = 0; t < HT; ++t) st_blk(mbuf, eid, D::HP, t, lane, m[t]);
+                for (int t = 0; t < HT; ++t) st_blk(mbuf, eid, D::HP, t, lane, m[t]);
+            }
         } else {
             // ---- S3: ew += SiLU(W3 m + b3); the next round's columns are fetched behind its barriers -------------------
             f4 pend[GP], pendz[TRAIN ? GP : 1];
@@ -268,8 +290,10 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
                 constexpr bool LAST = decltype(last_tag)::value;   // the last S3 phase (peeled): its post() fetches the next round's first edge-state blocks
                 auto post = [&]() {
                     if (p3 == 0) {
+                        if (!MSUM) {
 #pragma unroll
-                        for (int t = 0; t < HT; ++t) st_blk(mbuf, eid, D::HP, t, lane, m[t]);
+                            for (int t = 0; t < HT; ++t) st_blk(mbuf, eid, D::HP, t, lane, m[t]);
+                        }
                     } else {
 #pragma unroll
                         for (int gg = 0; gg < GP; ++gg) {
@@ -287,10 +311,13 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
                     }
                     if (nxt) {
                         if (p3 == 0) {                         // (with NP3 == 1 the blocks below wait for these: still one round trip saved)
-                            const size_t en = row_of(r + 1);
-                            src_n = tp.row_src[en]; tgt_n = tp.row_tgt[en]; eid_n = (size_t)tp.row_eid[en];
+                            if (MSUM) ci_n = info_of(r + 1);
+                            else {
+                                const size_t en = row_of(r + 1);
+                                src_n = tp.row_src[en]; tgt_n = tp.row_tgt[en]; eid_n = (size_t)tp.row_eid[en];
+                            }
                         }
-                        if (LAST) load_xn(xn_n, ew_in + row_of(r + 1) * D::WP + 4 * g);
+                        if (LAST) load_xn(xn_n, ew_in + rd_row(next_row()) * D::WP + 4 * g);
                     }
                 };
                 auto hook = [&]() { if (bar_left > 0 && --bar_left == 0) { PHASE_BARRIER(); post(); } pf.tick(); };
@@ -305,6 +332,7 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
                     }
                 }
                 if (bar_left > 0) { bar_left = 0; PHASE_BARRIER(); post(); }
+                if (MSUM && p3 == 0) st_msum<D>(mbuf, col_of(r), key, m, lane);      // (behind the chains, not in post(): see k_gcl_edge_v1)
                 pf.flush();
                 ++gp; ++lp;
             };
@@ -326,13 +354,15 @@ __global__ __launch_bounds__(512, 2) void k_gcl_edge_p(TopoDev tp, const float* 
 
         // ---- hand over to the next round -------------------------------------------------------------------------------
         if (nxt) {
-            set_rows(row_of(r + 1));
+            if (MSUM && !DO_S3) ci_n = info_of(r + 1);
+            set_rows(MSUM ? (size_t)ci_n.x : row_of(r + 1));
+            if (MSUM) { src = ci_n.y; tgt = ci_n.z; key = ci_n.w; }
             if (DO_S3) {                                       // indices and first edge-state blocks were fetched during S3
-                eid = eid_n; src = src_n; tgt = tgt_n;
+                if (!MSUM) { eid = eid_n; src = src_n; tgt = tgt_n; }
 #pragma unroll
                 for (int gg = 0; gg < GP; ++gg) xn[gg] = xn_n[gg];
             } else {                                           // no S3 to hide behind (last layer, inter-object rows)
-                eid = (size_t)tp.row_eid[e]; src = tp.row_src[e]; tgt = tp.row_tgt[e];
+                if (!MSUM) { eid = (size_t)tp.row_eid[e]; src = tp.row_src[e]; tgt = tp.row_tgt[e]; }
                 load_xn(xn, erow);
             }
             load_h1();

@@ -13,6 +13,7 @@
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
+typedef int i4 __attribute__((ext_vector_type(4)));
 
 // one 1-KiB chunk: per-lane global source, wave-uniform LDS destination (+ lane*16 by hardware)
 // timing-only ablations of an experiment build (results are garbage): OARD_ABL_NODMA_INSTR drops the LDS-DMA instruction and keeps
@@ -260,6 +261,61 @@ OARD_DEV f4 ld_edge(const float* p) { return (f4){0.25f, -0.5f, 0.125f, 1.0f}; }
 OARD_DEV f4 ld_edge(const float* p) { return ld_f4(p); }
 #endif
 
+// ---- per-node message sums inside the wave (MSUM instantiations) --------------------------------------------------------------
+// The columns of an MSUM launch are source-major (TopoDev::col_info): the messages a node aggregates sit in consecutive columns, and a
+// wave tile - the 16 lanes of one DPP row, four copies of it for the four feature slices g - holds at most 16 such runs ("segments").
+// Instead of one row of m per edge, the head lane of every segment stores the sum over its segment to msum[column of the head]; the
+// node stage adds the few partial rows of a node (k_gcl_node_v1<.., MSUM>).  The sum is a suffix scan over the row in four shift
+// steps (1, 2, 4, 8 lanes): after step d lane i holds the sum over lanes [i, i + 2d) of its segment, so which values are added in
+// which order depends on the lane positions of the segment alone.  key = source node + 1 (padding columns: -1): a shifted-in lane
+// outside the row reads as key 0 and matches nothing.  (The shifted values are read in EVERY lane and masked afterwards: a DPP read
+// inside a divergent branch sees the inactive lanes as 0.)
+template <int CTRL>
+OARD_DEV float dpp_row(float x) {                 // CTRL: 0x100 + d = row_shl:d (lane i reads lane i + d), 0x110 + d = row_shr:d; 0 outside the row
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
+}
+template <int CTRL>
+OARD_DEV int dpp_row_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true); }
+struct SegLanes {
+    float k1, k2, k4, k8;   // 1.0 where lane i + d belongs to this lane's segment, else 0.0
+    bool head;              // first lane of a segment of real columns: it stores the sum
+};
+OARD_DEV SegLanes seg_lanes(int key) {
+    SegLanes s;
+    s.k1 = dpp_row_i<0x101>(key) == key ? 1.f : 0.f; s.k2 = dpp_row_i<0x102>(key) == key ? 1.f : 0.f;
+    s.k4 = dpp_row_i<0x104>(key) == key ? 1.f : 0.f; s.k8 = dpp_row_i<0x108>(key) == key ? 1.f : 0.f;
+    const int prev = dpp_row_i<0x111>(key);               // (read in every lane, like the others)
+    s.head = key > 0 && prev != key;
+    return s;
+}
+// One step: v += (value of lane i + d) x (1 or 0) as ONE v_fmac_f32 with a DPP source - a multiplication, not a select: the sum of a
+// block is 16 VALU instructions (built from selects hipcc emits 48, and this wave's MFMA chains wait meanwhile); x 1.0 and + 0.0 are
+// exact.  It needs finite values in EVERY lane, padding columns included (0 x NaN): those compute on a real row's state (the kernels'
+// `erow`).  Written as one asm statement, so the wait states a DPP read needs are stated here: 2 behind a VALU write of the register it
+// reads (the four components are interleaved: three instructions between a component's steps; s_nop in front for the copies of m that
+// hipcc makes right before the statement), 5 behind a VALU write of EXEC (the same s_nop).  Lanes shifted in from outside the row read 0.
+OARD_DEV f4 seg_sum(f4 v, const SegLanes& s) {
+#define OARD_SEG_STEP(k, d) \
+        "v_fmac_f32_dpp %0, %0, " k " row_shl:" d " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_fmac_f32_dpp %1, %1, " k " row_shl:" d " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_fmac_f32_dpp %2, %2, " k " row_shl:" d " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+        "v_fmac_f32_dpp %3, %3, " k " row_shl:" d " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+    asm volatile("s_nop 4\n\t" OARD_SEG_STEP("%4", "1") OARD_SEG_STEP("%5", "2") OARD_SEG_STEP("%6", "4") OARD_SEG_STEP("%7", "8")
+                 : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w) : "v"(s.k1), "v"(s.k2), "v"(s.k4), "v"(s.k8));
+#undef OARD_SEG_STEP
+    return v;
+}
+// the 13 blocks of m: summed and stored one block at a time (four live registers, m itself stays what S3 multiplies)
+template <class D>
+OARD_DEV void st_msum(float* __restrict__ msum, long long col, int key, const f4 (&m)[D::HT], int lane) {
+    const SegLanes s = seg_lanes(key);
+#pragma unroll
+    for (int t = 0; t < D::HT; ++t) {
+        const f4 v = seg_sum(m[t], s);
+        if (s.head) st_blk(msum, (size_t)col, D::HP, t, lane, v);
+    }
+}
+
 template <class D, int GP>
 struct GclStream {
     static constexpr int HT = D::HT, WB = D::WB, G1 = HT, G2 = HT + 1, NG2 = HT + 1;
@@ -308,7 +364,9 @@ OARD_DEV float tail_compact(f4 v, int lane) {
 #ifndef OARD_BAR_AT
 #define OARD_BAR_AT 2
 #endif
-template <class D, int WAVES, int GP, bool DO_S1, bool DO_S3, bool TRAIN, int MINW = 2, int RING = 2>
+// MSUM (inference, 8-wave RING 3 shape): the columns [r0, r1) are entries of the source-major column list (TopoDev::col_info), r0 a
+//   multiple of 16, and `mbuf` is msum [columns + 1][HP]: per-node partial sums instead of one message row per edge (st_msum).
+template <class D, int WAVES, int GP, bool DO_S1, bool DO_S3, bool TRAIN, bool MSUM = false, int MINW = 2, int RING = 2>
 __global__ __launch_bounds__(WAVES * 64, MINW) void k_gcl_edge_v1(TopoDev tp, const float* __restrict__ stream,
                                                                const float* __restrict__ P, const float* __restrict__ Q,
                                                                const float* __restrict__ u0, const float* __restrict__ c0,
@@ -324,6 +382,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_gcl_edge_v1(TopoDev tp, co
     TL_DECL
     TL(0);
     static_assert(RING == 2 || RING == 3, "two slabs (barrier at the phase start) or three (barrier inside the phase)");
+    static_assert(!MSUM || !TRAIN, "the training-mode forward tapes agg from the per-edge message rows");
     static_assert(RING == 2 || HT >= 2, "the phase barrier must sit inside the FIRST chain of a phase (S3 stores the previous phase's results behind it)");
     constexpr int DIST = RING - 1;                             // phases the DMA runs ahead
     constexpr int BAR_AT = OARD_BAR_AT < HT / 2 ? OARD_BAR_AT : HT / 2;       // a chain over HT chunks has HT / 2 hook calls
@@ -353,13 +412,21 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_gcl_edge_v1(TopoDev tp, co
     // column of this lane; padding columns work on the spare row E of every per-edge buffer (allocated for that
     // purpose), so the kernel has no validity branches and every wave stays in the barrier protocol
     const long long c = r0 + ((long long)blockIdx.x * WAVES + wave) * 16 + (lane & 15);
-    const size_t e = (size_t)(c < r1 ? c : tp.E);
-    const float* erow = ew_in + e * D::WP + 4 * g;
+    // MSUM: row, source, target and segment key of the column come as one 16-byte table entry (no index load behind an index load)
+    i4 ci = {0, 0, 0, -1};
+    if (MSUM && c < r1) ci = *reinterpret_cast<const i4*>(tp.col_info + 4 * c);
+    const size_t e = (size_t)(c < r1 ? (MSUM ? (long long)ci.x : c) : tp.E);
+    // MSUM: padding columns READ the state of a real row (the launch's first column; their results still go to the spare row): the sums over
+    // the wave's columns multiply by 0 what they leave out, so every lane must hold finite values whatever the spare row contains
+    const size_t e_rd = (MSUM && e == (size_t)tp.E) ? (size_t)tp.col_info[4 * r0] : e;
+    const float* erow = ew_in + e_rd * D::WP + 4 * g;
     float* orow = ew_out + e * D::WP + 4 * g;
     f4 h1[HT];
-    const size_t eid = (size_t)tp.row_eid[e];                  // row of the message buffer (loaded here: its latency must not sit in S3)
+    const size_t eid = MSUM ? 0 : (size_t)tp.row_eid[e];       // row of the message buffer (loaded here: its latency must not sit in S3)
+    int key = 0;                                               // MSUM: segment key of this column (seg_lanes)
     {
-        const int src = tp.row_src[e], tgt = tp.row_tgt[e];
+        const int src = MSUM ? ci.y : tp.row_src[e], tgt = MSUM ? ci.z : tp.row_tgt[e];
+        if (MSUM) key = ci.w;
 #pragma unroll
         for (int t = 0; t < HT; ++t) {
             h1[t] = ld_blk(P, src, D::HP, t, lane) + ld_blk(Q, tgt, D::HP, t, lane);
@@ -484,8 +551,11 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_gcl_edge_v1(TopoDev tp, co
     // stores are issued one phase late (right after the next barrier) so that the barrier's vmcnt(0)
     // never waits for a store that was issued a few cycles earlier
     if (!DO_S3) {
+        if (MSUM) st_msum<D>(mbuf, c, key, m, lane);
+        else {
 #pragma unroll
-        for (int t = 0; t < HT; ++t) st_blk(mbuf, eid, D::HP, t, lane, m[t]);
+            for (int t = 0; t < HT; ++t) st_blk(mbuf, eid, D::HP, t, lane, m[t]);
+        }
         PROBE_END(pf);
         TL_END();
         return;
@@ -496,8 +566,10 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_gcl_edge_v1(TopoDev tp, co
         auto post = [&]() {
             TL(1);
             if (p3 == 0) {
+                if (!MSUM) {
 #pragma unroll
-                for (int t = 0; t < HT; ++t) st_blk(mbuf, eid, D::HP, t, lane, m[t]);
+                    for (int t = 0; t < HT; ++t) st_blk(mbuf, eid, D::HP, t, lane, m[t]);
+                }
             } else {
 #pragma unroll
                 for (int gg = 0; gg < GP; ++gg) {              // (p3-1)*GP+gg < WB always
@@ -530,6 +602,10 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_gcl_edge_v1(TopoDev tp, co
         }
         TL(4);
         if (RING == 3 && bar_left > 0) { bar_left = 0; PHASE_BARRIER(); post(); }
+        // MSUM: the per-node sums leave behind the chains of the first S3 phase, a phase ahead of the next barrier's vmcnt(0) like the row
+        // stores they replace - and NOT inside post(): the DPP reads are convergent operations, and with them in the hook hipcc no longer
+        // resolves bar_left at compile time (a copy of post() behind every MFMA pair: 12 x the code, 720 bytes of scratch)
+        if (MSUM && p3 == 0) st_msum<D>(mbuf, c, key, m, lane);
         pf.flush();
         ++p;
     };

@@ -79,6 +79,8 @@ int g_auto_small = 4;       // 1: small launches use the 4-wave workgroups (one 
 int g_npb = 0;              // nodes per workgroup of the node stages (0 = auto, see oard_topology_create)
 int g_poison = 0;           // 1: fill the workspace with NaN bit patterns before every forward (tests: nothing may depend on its contents)
 int g_equi_l0_skip = 1;     // 0: layer 0 runs the whole EquiMessage like every other layer (A/B and tests; see forward_impl, l0_skip)
+int g_gcl_msum = 1;         // 0: the GCL edge kernels store one message row per edge and the node stage gathers them (A/B and tests; forward_impl, msum)
+int g_gcl_msum_taken = 0;   // did the last forward sum the messages inside the edge kernels (tests: oard_debug_option("gcl_msum_taken", 0) == OARD_OK)
 int g_equi_l0_taken = 0;    // did the last forward take that shortcut (tests: oard_debug_option("equi_l0_taken", 0) == OARD_OK)
 int g_parts = 0;            // sub-batches per topology (0 = auto: 4 for B >= 32, 2 for B >= 16, else 1)
 int g_small_split = 128;     // EquiMessage latency kernel: launches of <= this many 16-edge tiles run one launch per dense stage
@@ -328,7 +330,9 @@ static WsOff make_ws(const oard_config* c, const TopoDev& td) {
     w.xq = take(N * 3 * d.HP * 4); w.vec = take(N * 3 * d.HP * 4); w.vec2 = take(N * 3 * d.HP * 4); w.v2buf = take(N * 3 * d.HP * 4);
     w.sc0 = take(N * d.HP * 4); w.vdot = take(N * d.HP * 4);
     w.geo = take(A * GEO_STRIDE * 4); w.d64 = take(A * 8); w.rbuf = take(A * d.RP * 4);
-    w.ew = take(E * d.WP * 4); w.mbuf = take(E * d.HP * 4);
+    // mbuf [E + 1][HP]: one message row per edge - or, in its place, msum [CI + CX + 1][HP]: the per-node partial sums, indexed by column
+    // (forward_impl, msum); never zero-filled: the node stage reads what the edge kernels of the same layer wrote
+    w.ew = take(E * d.WP * 4); w.mbuf = take(std::max(E, (size_t)(td.CI + td.CX) + 1) * d.HP * 4);
     w.xmsg = take(A * d.HP * 4); w.vmsg = take(A * 3 * d.HP * 4);
     w.dpos = take(N * 3 * 4); w.hout = take(N * 16 * 4);
     // scratch of the stage-split latency edge kernels: only topologies small enough to ever take that path (the launch-shape
@@ -364,7 +368,7 @@ int set_lds(K kernel, size_t bytes) {
                    (GclStream<D, GP_>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
 // the throughput shape: 8 waves x 16 edges, two waves per SIMD, three LDS slabs (barrier inside the phase)
 #define GCL_RING3(TRAIN_, tape_) do { \
-        LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 8, 2, S1, S3, TRAIN_, 2, 3>), cdiv(r1 - r0, 16 * 8), 8 * 64, \
+        LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 8, 2, S1, S3, TRAIN_, false, 2, 3>), cdiv(r1 - r0, 16 * 8), 8 * 64, \
                    (GclStream<D, 2>::LDS_BYTES / 2 * 3), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, tape_); return OARD_OK; } while (0)
 static int device_cus() {
     static int cus[64] = {};
@@ -378,10 +382,19 @@ static int device_cus() {
     }
     return cus[d];
 }
+// does an inference launch over `cols` columns take the streamed fp32 throughput shape - the 8-wave tile kernel or the persistent one
+// (launch_gcl_v1s decides the same way; forward_impl asks for every launch of a call before it lets the edge kernels sum the messages)
+static bool gcl_v1_throughput(int prec, int variant, int conc, long long cols) {
+    if (variant == 2 && cdiv(cols, 16) * conc <= 1024LL * g_auto_small) variant = 3;
+    if ((variant == 2 || variant == 3) && cdiv(cols, 16) * conc <= 512LL * g_auto_tiny) variant = 6;
+    return variant == 2 && !(prec & OARD_PREC_GCL_BF16X3);
+}
 template <class D, bool S1, bool S3>
 int launch_gcl_v1s(int prec, int variant, int conc, const TopoDev& tp, const float* wb, const LayerOff& lo, const float* stream, const float* P, const float* Q, const float* u0,
-                   const float* c0, long long r0, long long r1, const float* ew_in, float* ew_out, float* mbuf, const GclTape* tape, hipStream_t st) {
+                   const float* c0, long long r0, long long r1, const float* ew_in, float* ew_out, float* mbuf, const GclTape* tape, hipStream_t st,
+                   bool msum = false) {
     if (r1 <= r0) return OARD_OK;
+    if (msum && (tape || !gcl_v1_throughput(prec, variant, conc, r1 - r0))) return OARD_EINVAL;      // (forward_impl asked the same function)
     if (tape && (prec & OARD_PREC_TRAIN_BF16X3)) {    // training-mode forward in split precision (optional)
         LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_b3<D, S1, S3, true>), cdiv(r1 - r0, 16 * 8), 8 * 64, (GclB3Stream<D>::LDS_BYTES), st, tp,
                    wb + lo.gcl_b3, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, *tape);
@@ -426,8 +439,18 @@ int launch_gcl_v1s(int prec, int variant, int conc, const TopoDev& tp, const flo
                 const long long nhalf = cdiv(cdiv(r1 - r0, 16), 4);
                 // gcl_grid < 0: -k = k rounds (128-row tiles) per workgroup
                 const long long want = g_gcl_grid > 0 ? g_gcl_grid : (g_gcl_grid < 0 ? cdiv(nhalf, 2LL * -g_gcl_grid) : (conc > 1 ? std::max(1, device_cus() / 2) : device_cus()));
+                if (msum) {
+                    LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_p<D, S1, S3, false, true>), std::min(nhalf, want), 8 * 64, (GclStream<D, 2>::LDS_BYTES / 2 * 3), st,
+                               tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{});
+                    return OARD_OK;
+                }
                 LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_p<D, S1, S3>), std::min(nhalf, want), 8 * 64, (GclStream<D, 2>::LDS_BYTES / 2 * 3), st,
                            tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{});
+                return OARD_OK;
+            }
+            if (msum) {
+                LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 8, 2, S1, S3, false, true, 2, 3>), cdiv(r1 - r0, 16 * 8), 8 * 64,
+                           (GclStream<D, 2>::LDS_BYTES / 2 * 3), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{});
                 return OARD_OK;
             }
             GCL_RING3(false, GclTape{});
@@ -442,11 +465,11 @@ int launch_gcl_v1s(int prec, int variant, int conc, const TopoDev& tp, const flo
                        (GclRing<D, 2, 3>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
         GCL_CASE(8, 8, 3)
         GCL_CASE(9, 8, 4)
-        case 10: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 12, 1, S1, S3, false, 3>), cdiv(r1 - r0, 16 * 12), 12 * 64,
+        case 10: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 12, 1, S1, S3, false, false, 3>), cdiv(r1 - r0, 16 * 12), 12 * 64,
                               (GclStream<D, 1>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
-        case 11: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 12, 2, S1, S3, false, 3>), cdiv(r1 - r0, 16 * 12), 12 * 64,
+        case 11: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 12, 2, S1, S3, false, false, 3>), cdiv(r1 - r0, 16 * 12), 12 * 64,
                               (GclStream<D, 2>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
-        case 12: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 4, 1, S1, S3, false, 3>), cdiv(r1 - r0, 16 * 4), 4 * 64,
+        case 12: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 4, 1, S1, S3, false, false, 3>), cdiv(r1 - r0, 16 * 4), 4 * 64,
                               (GclStream<D, 1>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
 #endif
         default: return OARD_EINVAL;
@@ -456,10 +479,25 @@ int launch_gcl_v1s(int prec, int variant, int conc, const TopoDev& tp, const flo
 // layer (constant initial state) and S3 in the last (their updated state is never read)
 template <class D>
 int launch_gcl_v1(int prec, int variant, int conc, const TopoDev& tp, const float* wb, const LayerOff& lo, const float* stream, const float* P, const float* Q, const float* u0,
-                  const float* c0, bool first, bool last, const float* ew_in, float* ew_out, float* mbuf, const GclTape* tape, hipStream_t st) {
+                  const float* c0, bool first, bool last, const float* ew_in, float* ew_out, float* mbuf, const GclTape* tape, hipStream_t st,
+                  bool msum = false) {
     const long long A = tp.A, E = tp.E;
     int rc;
     const bool skip = g_gcl_skip || tape;
+    if (msum) {
+        // the edge kernels sum the messages per node: every layer runs the inner and the inter-object columns of the source-major list
+        // (TopoDev::col_info), `mbuf` is msum
+        const long long c_in = tp.CI, c_all = tp.CI + tp.CX;
+        const bool s1 = !(skip && first), s3 = !(skip && last);
+        // (where both lists run every stage they are ONE launch: the inter-object list starts on a multiple of 16 columns, so the wave tiles
+        // - and with them every partial sum - are the same as in two launches)
+        if (s1 && s3) return launch_gcl_v1s<D, true, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, 0, c_all, ew_in, ew_out, mbuf, tape, st, true);
+        rc = launch_gcl_v1s<D, true, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, 0, c_in, ew_in, ew_out, mbuf, tape, st, true);
+        if (rc != OARD_OK) return rc;
+        if (s1) return launch_gcl_v1s<D, true, false>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, c_in, c_all, ew_in, ew_out, mbuf, tape, st, true);
+        if (s3) return launch_gcl_v1s<D, false, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, c_in, c_all, ew_in, ew_out, mbuf, tape, st, true);
+        return launch_gcl_v1s<D, false, false>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, c_in, c_all, ew_in, ew_out, mbuf, tape, st, true);
+    }
     if (!skip || (!first && !last)) return launch_gcl_v1s<D, true, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, 0, E, ew_in, ew_out, mbuf, tape, st);
     rc = launch_gcl_v1s<D, true, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, 0, A, ew_in, ew_out, mbuf, tape, st);
     if (rc != OARD_OK) return rc;
@@ -646,6 +684,14 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
     float* vec2 = (float*)(ws + w.vec2);
     float* vcur = vec;          // holds the current vec; v1 ping-pongs between vec and vec2
     float* vnext = vec2;
+    // GCL messages summed per node inside the edge kernels (st_msum) and ~6 partial rows per node gathered instead of one row per edge:
+    // decided once per call and sub-batch, both kernels or neither - only if EVERY GCL launch of the call takes the streamed fp32
+    // throughput shape (8-wave tile or persistent kernel) and the node stage is the large-batch one.  The training-mode forward tapes agg
+    // and keeps the message rows.
+    const bool msum = !train && g_gcl_msum && E > 0 && gcl_variant == 2 && node_variant == 1 && equi_variant != 0 && tp.npb > 4 &&
+                      (tp.CI == 0 || gcl_v1_throughput(c->precision, gcl_variant, topo->conc, tp.CI)) &&
+                      (tp.CX == 0 || gcl_v1_throughput(c->precision, gcl_variant, topo->conc, tp.CX));      // (the smaller launches decide)
+    g_gcl_msum_taken = msum;
     for (int l = 0; l < c->num_layers; ++l) {
         const LayerOff lo = po.layer[l];
         const bool nv1 = node_variant == 1 && equi_variant != 0;
@@ -665,13 +711,15 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
                 GclTape gt{};
                 if (train) gt = GclTape{(float*)(tape + to.z1[l]), (float*)(tape + to.z2[l]), (float*)(tape + to.att[l]), (float*)(tape + to.z3[l])};
                 int rc = launch_gcl_v1<D>(c->precision, gcl_variant, topo->conc, tp, wb, lo, wb + lo.gcl_stream, P, Q, wb + po.u0, wb + po.c0row, l == 0,
-                                          l == c->num_layers - 1, ew_in, ew_out, mbuf, train ? &gt : nullptr, st);
+                                          l == c->num_layers - 1, ew_in, ew_out, mbuf, train ? &gt : nullptr, st, msum);
                 if (rc != OARD_OK) return rc;
             }
         }
         const bool rows = tp.npb <= 4;                       // small batches: gathers walk the rows with the wave's columns (row_lanes)
         if (nv1 && rows) LAUNCH(F_NODE, (k_gcl_node_v1<D, NW, true>), gN16, NW * 64, st, tp, wb, lo, (const float*)xhb, (const float*)mbuf, s_mid_at(l), xq,
                                 train ? (float*)(tape + to.agg[l]) : nullptr);
+        else if (nv1 && msum) LAUNCH(F_NODE, (k_gcl_node_v1<D, NW, false, true>), gN16, NW * 64, st, tp, wb, lo, (const float*)xhb, (const float*)mbuf, s_mid_at(l), xq,
+                                     (float*)nullptr);
         else if (nv1) LAUNCH(F_NODE, (k_gcl_node_v1<D, NW, false>), gN16, NW * 64, st, tp, wb, lo, (const float*)xhb, (const float*)mbuf, s_mid_at(l), xq,
                              train ? (float*)(tape + to.agg[l]) : nullptr);
         else if constexpr (kV0) LAUNCH(F_NODE, (k_gcl_node<D>), gN, 256, st, tp, wb, lo, (const float*)xhb, (const float*)mbuf, s, xq);
@@ -1296,6 +1344,42 @@ static int build_part(const oard_config* c, const int64_t* cm, const int64_t* nf
     }
     std::vector<long long> ref_edge_ptr(N);
     for (int n = 0; n < N; ++n) ref_edge_ptr[n] = ref_ptr_ref[node_ref[n]];
+    // GCL columns, source-major (TopoDev::col_info): per reaction the inner rows of every node as SOURCE, in target order, then - in
+    // the second list - its inter-object rows in logical order; both lists start every reaction on a multiple of 16 columns
+    std::vector<int> col_row, col_info, node_cols((size_t)N * 4, 0);
+    long long CI = 0, CX = 0;
+    {
+        auto pad16 = [&]() { while (col_row.size() % 16) col_row.push_back((int)E); };
+        for (int b = 0; b < B; ++b) {
+            for (int n = sample_ptr[b]; n < sample_ptr[b + 1]; ++n) {
+                const int q = node_sample[n] * n_obj + node_obj[n];
+                const int g0 = grp_ptr[q], g1 = grp_ptr[q + 1];
+                node_cols[4 * (size_t)n + 0] = (int)col_row.size();
+                for (int m = g0; m < g1; ++m) if (m != n) col_row.push_back(act_ptr[m] + (n - g0) - (n > m ? 1 : 0));
+                node_cols[4 * (size_t)n + 1] = (int)col_row.size();
+            }
+            pad16();
+        }
+        CI = (long long)col_row.size();
+        for (int b = 0; b < B; ++b) {
+            const int ns = sample_ptr[b + 1] - sample_ptr[b];
+            for (int n = sample_ptr[b]; n < sample_ptr[b + 1]; ++n) {
+                node_cols[4 * (size_t)n + 2] = (int)col_row.size();
+                for (long long e = edge_ptr[n]; e < (long long)edge_ptr[n] + ns - 1; ++e) if (edge_row[e] >= A) col_row.push_back(edge_row[e]);
+                node_cols[4 * (size_t)n + 3] = (int)col_row.size();
+            }
+            pad16();
+        }
+        CX = (long long)col_row.size() - CI;
+        if (CI + CX > 0x7fffffffLL - 256) return OARD_EINVAL;
+        if (col_row.empty()) col_row.push_back((int)E);
+        col_info.resize(col_row.size() * 4);
+        for (size_t k = 0; k < col_row.size(); ++k) {
+            const int r = col_row[k];
+            col_info[4 * k] = r; col_info[4 * k + 1] = row_src[r]; col_info[4 * k + 2] = row_tgt[r];
+            col_info[4 * k + 3] = r == (int)E ? -1 : row_src[r] + 1;
+        }
+    }
 
     std::vector<UploadItem> items;
     size_t cur = 0;
@@ -1308,7 +1392,8 @@ static int build_part(const oard_config* c, const int64_t* cm, const int64_t* nf
                  o_asrc = add(act_src.data(), act_src.size() * 4), o_atgt = add(act_tgt.data(), act_tgt.size() * 4),
                  o_aedge = add(act_edge.data(), act_edge.size() * 4), o_rptr = add(ref_edge_ptr.data(), N * 8),
                  o_erow = add(edge_row.data(), edge_row.size() * 4), o_rsrc = add(row_src.data(), row_src.size() * 4),
-                 o_rtgt = add(row_tgt.data(), row_tgt.size() * 4), o_reid = add(row_eid.data(), row_eid.size() * 4);
+                 o_rtgt = add(row_tgt.data(), row_tgt.size() * 4), o_reid = add(row_eid.data(), row_eid.size() * 4),
+                 o_crow = add(col_info.data(), col_info.size() * 4), o_ncol = add(node_cols.data(), node_cols.size() * 4);
     size_t cap = 0;
     char* dev = (char*)pool_alloc(cur, &cap);
     if (!dev) return OARD_EHIP;
@@ -1325,6 +1410,7 @@ static int build_part(const oard_config* c, const int64_t* cm, const int64_t* nf
     d.ref_edge_ptr = (const long long*)(dev + o_rptr);
     d.edge_row = (const int*)(dev + o_erow); d.row_src = (const int*)(dev + o_rsrc); d.row_tgt = (const int*)(dev + o_rtgt);
     d.row_eid = (const int*)(dev + o_reid);
+    d.CI = CI; d.CX = CX; d.col_info = (const int*)(dev + o_crow); d.node_cols = (const int*)(dev + o_ncol);
     return OARD_OK;
 }
 
@@ -2330,6 +2416,8 @@ int oard_debug_option(const char* name, int value) {
     if (strcmp(name, "gcl_skip") == 0) { g_gcl_skip = value; return OARD_OK; }
     if (strcmp(name, "equi_skip") == 0) { g_equi_skip = value; return OARD_OK; }
     if (strcmp(name, "equi_l0_skip") == 0) { g_equi_l0_skip = value; return OARD_OK; }
+    if (strcmp(name, "gcl_msum") == 0) { g_gcl_msum = value; return OARD_OK; }
+    if (strcmp(name, "gcl_msum_taken") == 0) return g_gcl_msum_taken ? OARD_OK : OARD_EINVAL;      // query: did the last forward take that form?
     if (strcmp(name, "equi_l0_taken") == 0) return g_equi_l0_taken ? OARD_OK : OARD_EINVAL;      // query: did the last forward skip it?
     if (strcmp(name, "gcl_persist") == 0) { g_gcl_persist = value; return OARD_OK; }
     if (strcmp(name, "gcl_grid") == 0) { g_gcl_grid = value; return OARD_OK; }

@@ -24,7 +24,8 @@
 
 // ---- k_gcl_edge_p: persistent GCL throughput shape, inference and training-mode (oard_edge_p.h) --------------------------------------
 #if !defined(OARD_INST_DEFINE) || defined(OARD_INST_UNIT_GCL_P)
-#define OARD_I_GCL_P(D, S1, S3) OARD_INST((k_gcl_edge_p<OARD_UNPAREN D, S1, S3, false>), OARD_A_GCL) OARD_INST((k_gcl_edge_p<OARD_UNPAREN D, S1, S3, true>), OARD_A_GCL)
+#define OARD_I_GCL_P(D, S1, S3) OARD_INST((k_gcl_edge_p<OARD_UNPAREN D, S1, S3, false>), OARD_A_GCL) OARD_INST((k_gcl_edge_p<OARD_UNPAREN D, S1, S3, true>), OARD_A_GCL) \
+    OARD_INST((k_gcl_edge_p<OARD_UNPAREN D, S1, S3, false, true>), OARD_A_GCL)
 #define X(h, r) OARD_BOOL4(OARD_I_GCL_P, (Dims<h, r>))
 OARD_DIMS_LIST
 #undef X
@@ -33,8 +34,9 @@ OARD_DIMS_LIST
 // ---- k_gcl_edge_v1 (8-wave ring-3 shape: inference + training-mode; 4-wave shape), k_gcl_edge_small (oard_edge_v1.h, oard_edge_small.h) ---
 #if !defined(OARD_INST_DEFINE) || defined(OARD_INST_UNIT_GCL_V1)
 #define OARD_I_GCL_V1(D, S1, S3) \
-    OARD_INST((k_gcl_edge_v1<OARD_UNPAREN D, 8, 2, S1, S3, false, 2, 3>), OARD_A_GCL) OARD_INST((k_gcl_edge_v1<OARD_UNPAREN D, 8, 2, S1, S3, true, 2, 3>), OARD_A_GCL) \
-    OARD_INST((k_gcl_edge_v1<OARD_UNPAREN D, 4, 2, S1, S3, false, 2, 2>), OARD_A_GCL) \
+    OARD_INST((k_gcl_edge_v1<OARD_UNPAREN D, 8, 2, S1, S3, false, false, 2, 3>), OARD_A_GCL) OARD_INST((k_gcl_edge_v1<OARD_UNPAREN D, 8, 2, S1, S3, true, false, 2, 3>), OARD_A_GCL) \
+    OARD_INST((k_gcl_edge_v1<OARD_UNPAREN D, 8, 2, S1, S3, false, true, 2, 3>), OARD_A_GCL) \
+    OARD_INST((k_gcl_edge_v1<OARD_UNPAREN D, 4, 2, S1, S3, false, false, 2, 2>), OARD_A_GCL) \
     OARD_INST((k_gcl_edge_small<OARD_UNPAREN D, 8, S1, S3>), (TopoDev, const float*, LayerOff, const float*, const float*, const float*, const float*, long long, long long, float*, float*))
 #define X(h, r) OARD_BOOL4(OARD_I_GCL_V1, (Dims<h, r>))
 OARD_DIMS_LIST
@@ -76,6 +78,7 @@ OARD_DIMS_LIST
 #define OARD_A_MSG_BWD (TopoDev, const float*, Strided3, Strided3, const float*, Strided3, const float*, int, Strided3, float*, float*, float*, float*, int, int, int)
 #define X(h, r) \
     OARD_INST((k_gcl_node_v1<Dims<h, r>, OARD_NW(h), false>), OARD_A_GCL_NODE) OARD_INST((k_gcl_node_v1<Dims<h, r>, OARD_NW(h), true>), OARD_A_GCL_NODE) \
+    OARD_INST((k_gcl_node_v1<Dims<h, r>, OARD_NW(h), false, true>), OARD_A_GCL_NODE) \
     OARD_INST((k_out_v1<Dims<h, r>, OARD_NW(h)>), OARD_A_OUT) \
     OARD_INST((k_scalarize_bwd<Dims<h, r>, 2, false>), OARD_A_SCAL_BWD) OARD_INST((k_scalarize_bwd<Dims<h, r>, 2, true>), OARD_A_SCAL_BWD) \
     OARD_INST((k_equi_msg_bwd<Dims<h, r> >), OARD_A_MSG_BWD)

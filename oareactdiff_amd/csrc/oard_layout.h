@@ -86,6 +86,14 @@ struct TopoDev {
     const int *grp_ptr;                       // [n_groups+1], group q = sample*n_obj + obj
     const int *act_ptr, *act_src, *act_tgt, *act_edge;
     const long long *ref_edge_ptr;            // [N] first reference-order edge of internal node n
+    // GCL columns in SOURCE-major order (gcl_msum: the edge kernel sums the messages of a node inside the wave): the inner list
+    // [0, CI) - the rows above are target-sorted for EquiMessage -, then the inter-object list [CI, CI + CX).  Every reaction's block
+    // starts on a multiple of 16 columns in both lists (CI, CX count the padding), so where a node's columns fall inside a 16-column
+    // wave tile is a property of its reaction alone.
+    long long CI, CX;
+    const int *col_info;                      // [CI + CX][4] column -> (physical row, source node, target node, segment key = source + 1);
+                                              //   padding columns -> (the spare row E, 0, 0, -1).  One 16-byte load, no dependent index loads
+    const int *node_cols;                     // [N][4]   columns of node n: inner [lo, hi), inter [lo, hi)
 };
 
 // Inner (same-object) edges whose distance is inside the cutoff, compacted once per forward call (k_active_list): EquiMessage is

@@ -354,11 +354,16 @@ __global__ __launch_bounds__(WAVES * 64) void k_node_pre_v1(TopoDev tp, const fl
 // agg = mean_e m_e;  s = xh + node_mlp([xh, agg]);  xq = x_proj(LN_msg(s))           (see k_gcl_node)
 // =====================================================================================================
 // ROWS: the small-batch gather (row_lanes, <= 4 nodes per workgroup) - its own instantiation, chosen at launch
-template <class D, int WAVES, bool ROWS = false>
+// MSUM (large batches only): `mbuf` is msum, the per-node partial sums the MSUM edge kernels left (oard_edge_v1.h, st_msum) - one at the
+//   first column of each of the node's two column ranges (TopoDev::node_cols) and one at every multiple of 16 strictly inside a range,
+//   where a wave tile cut the node's segment.  They are added in ascending column order, inner range first: ~6 rows per node instead of
+//   one per edge.  Its own instantiation, the others stay what they are.
+template <class D, int WAVES, bool ROWS = false, bool MSUM = false>
 __global__ __launch_bounds__(WAVES * 64) void k_gcl_node_v1(TopoDev tp, const float* __restrict__ wb, LayerOff lo,
                                                             const float* __restrict__ xh, const float* __restrict__ mbuf,
                                                             float* __restrict__ s, float* __restrict__ xq,
                                                             float* __restrict__ agg_out /* training tape, or NULL */) {
+    static_assert(!(MSUM && ROWS), "the partial sums exist for the large-batch gather only");
     __shared__ __attribute__((aligned(16))) float sm[4 * D::HT * 256];
     float* in = sm;                        // [2 HT]: xh | agg      (later: xln | hq)
     float* hm = sm + 2 * D::HT * 256;      // [HT]
@@ -369,6 +374,20 @@ __global__ __launch_bounds__(WAVES * 64) void k_gcl_node_v1(TopoDev tp, const fl
     const size_t e0 = (size_t)tp.edge_ptr[nb.n];
     const int mx = wave_max(deg);
     const float inv = 1.0f / (float)max(deg, 1);
+    // MSUM: partial k of the node = column pc(k); n_in of them in the inner range, cnt in all
+    int in_lo = 0, x_lo = 0, n_in = 0, cnt = 0;
+    if (MSUM) {
+        const int* nc = tp.node_cols + 4 * (size_t)nb.n;
+        const int in_hi = nc[1], x_hi = nc[3];
+        in_lo = nc[0]; x_lo = nc[2];
+        n_in = (nb.valid && in_hi > in_lo) ? 1 + ((in_hi - 1) >> 4) - (in_lo >> 4) : 0;
+        cnt = n_in + ((nb.valid && x_hi > x_lo) ? 1 + ((x_hi - 1) >> 4) - (x_lo >> 4) : 0);
+    }
+    auto pc = [&](int k) -> size_t {
+        const int lo = k < n_in ? in_lo : x_lo, j = k < n_in ? k : k - n_in;
+        return (size_t)(j == 0 ? lo : ((lo >> 4) + j) << 4);
+    };
+    const int mxp = MSUM ? wave_max(cnt) : 0;
     for (int t = nb.wave; t < D::HT; t += WAVES) {
         lds_st(in, t, nb.lane, ld_blk(xh, nb.n, D::HP, t, nb.lane));
         f4 a0 = f4zero(), a1 = f4zero();
@@ -390,7 +409,17 @@ __global__ __launch_bounds__(WAVES * 64) void k_gcl_node_v1(TopoDev tp, const fl
         }
         // 8 message rows in flight per step (branch-free: out-of-range slots re-read the last row with weight 0)
         const int last = max(deg - 1, 0);
-        for (int k = 0; !ROWS && k < mx; k += 8) {
+        for (int k = 0; MSUM && k < mxp; k += 8) {            // 8 partial rows in flight (slots past the end re-read the last one with weight 0)
+            f4 r[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) r[i] = ld_blk(mbuf, pc(min(k + i, max(cnt - 1, 0))), D::HP, t, nb.lane);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const f4 v = k + i < cnt ? r[i] : f4zero();
+                if (i & 1) a1 += v; else a0 += v;
+            }
+        }
+        for (int k = 0; !ROWS && !MSUM && k < mx; k += 8) {
             f4 r[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) r[i] = ld_blk(mbuf, e0 + min(k + i, last), D::HP, t, nb.lane);
