@@ -89,6 +89,22 @@ def test_fused_equals_autograd_off_the_fixtures():
     _fused_against_autograd(trainer, reps, torch.zeros(b.B, 1, device=dev), t_int, draws, "off the fixtures")
 
 
+def test_fused_equals_autograd_on_unequal_objects():
+    """The same comparison on the `mixed` batch of tests/_grad_cases.py: the three objects of a reaction differ in size (1 ... 33
+    atoms), production widths, t = 0 and t = T live.  tests/test_grad_ragged.py holds the autograd formulation on this batch
+    against the float64 oracle, so this ties the fused sweep to that reference too."""
+    from _grad_cases import SyntheticGradCase
+    c = SyntheticGradCase("mixed", references=False)
+    dev = torch.device("cuda:0")
+    t_int = torch.tensor(c.meta["t_int"], dtype=torch.float32, device=dev).view(-1, 1)
+
+    def draws():
+        it = iter(c.draws)
+        return lambda shape: next(it).to(dev)
+    _fused_against_autograd(lambda fused: _trainer(c, dev, fused, False), lambda: c.reps(torch.float32, dev),
+                            torch.zeros(c.B, 1, device=dev), t_int, draws, "mixed (unequal objects)")
+
+
 def test_fused_step_runs_and_moves_the_weights():
     c = GradCase("g9_grad_h32")
     dev = torch.device("cuda:0")
