@@ -24,6 +24,7 @@
 #include "oard_edge_bwd.h"
 #include "oard_node_bwd.h"
 #include "oard_rows.h"
+#include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
 #define OARD_VERSION 2040      // round 6: + oard_graph_* (general edge lists), oard_library_stream
@@ -69,33 +70,18 @@ struct Timing {
     }
 } g_timing;
 int g_stop_after = 0;
-int g_gcl_variant = 2;     // 0: v0 (weights straight from L2), 2: LDS-streamed 8-wave shape, 3: 4-wave shape, 6: latency kernel
-int g_equi_variant = 2;    // 0: v0, 2: LDS-streamed 8-wave shape, 1: 4-wave shape, 4: latency kernel
+FwdOptions g_fwd;           // the forward-shape options (oard_plan.h); a call plans every sub-batch from ONE copy of it
 int g_sequential = 0;       // 1: run the sub-batches one after the other on the caller stream (profiling)
-int g_auto_tiny = 8;        // launches of <= 512 * g_auto_tiny edge tiles (all concurrent sub-batches together) use the
-                            //    latency kernels of oard_edge_small.h (8 waves share 16 edges); 0 = never
-int g_auto_small = 4;       // 1: small launches use the 4-wave workgroups (one wave per SIMD instead of two): a launch that cannot
-                            //    fill the chip anyway finishes sooner when its waves do not share a SIMD (B <= 8 reactions: -25 %)
 int g_npb = 0;              // nodes per workgroup of the node stages (0 = auto, see oard_topology_create)
 int g_poison = 0;           // 1: fill the workspace with NaN bit patterns before every forward (tests: nothing may depend on its contents)
-int g_equi_l0_skip = 1;     // 0: layer 0 runs the whole EquiMessage like every other layer (A/B and tests; see forward_impl, l0_skip)
-int g_gcl_msum = 1;         // 0: the GCL edge kernels store one message row per edge and the node stage gathers them (A/B and tests; forward_impl, msum)
 int g_gcl_msum_taken = 0;   // did the last forward sum the messages inside the edge kernels (tests: oard_debug_option("gcl_msum_taken", 0) == OARD_OK)
 int g_equi_l0_taken = 0;    // did the last forward take that shortcut (tests: oard_debug_option("equi_l0_taken", 0) == OARD_OK)
 int g_parts = 0;            // sub-batches per topology (0 = auto: 4 for B >= 32, 2 for B >= 16, else 1)
-int g_small_split = 128;     // EquiMessage latency kernel: launches of <= this many 16-edge tiles run one launch per dense stage
-                            // (a workgroup = 16 edges x 8 output tiles); 0 = never
 int g_wgrad_shapes = 3;       // bit k: workgroup shape kWglShapes[k] of the LDS-panel kernel may be chosen (A/B: debug option wgrad_shapes)
 int g_wgrad_t16 = 256;       // workgroups per weight-gradient GEMM of the 16 x 16-tile kernel (oard_wgrad_t16.h; 0: never use it)
 int g_wgrad_lds = 256;       // workgroups per weight-gradient GEMM of the LDS-panel kernel (0: always the per-wave-tile kernel k_wgrad)
 int g_wgrad_wgs = 512;       // workgroups per weight-gradient GEMM (row chunks x task groups): one round of 2 x 4 waves per CU
                             // (measured per training step: 384 -> 38.1 ms, 512 -> 30.7, 768 -> 36.0, 1024 -> 33.2, 2048 -> 38.1)
-int g_gcl_persist = 1;      // the fp32 GCL throughput shape as a persistent workgroup (oard_edge_p.h); 0: one 128-edge tile per workgroup
-int g_gcl_grid = 0;         // workgroups per launch of the persistent kernel: 0 = auto (one per CU when the launch has the chip to itself,
-                            //    half of them when sub-batches run concurrently), > 0 = that many
-int g_equi_skip = 1;        // EquiMessage runs the inner edges inside the cutoff only (ActList; exact: it is zero on the others).  0: every inner row
-int g_gcl_skip = 1;         // skip S1 (first layer) / S3 (last layer) on inter-object edges
-int g_node_variant = 1;     // 0: one wave per 16 nodes, 1: 8 waves per 16 nodes with LDS-resident activations
 // Arithmetic of the two MFMA edge stages: oard_config::precision (OARD_PREC_* bits, include/oard.h) - a property of the CALL, read
 // when the weights are packed (the bf16 streams are only built for the bits set) and when the stages are launched.  There is no
 // process-wide precision state: two modules with different precision may run from two threads / on two streams.
@@ -313,10 +299,8 @@ struct Packer {
         return OARD_OK;
     }
 };
-// scratch of the stage-split latency path (activations between the stage launches), set per forward call / sub-batch
+// scratch of the stage-split latency path (activations between the stage launches)
 #define OARD_SMALL_MAX_EDGES (512 * 16 * 16)      // topologies up to 131 072 edges get the scratch buffer
-struct SmallScratch { float* a; float* b; };
-static thread_local SmallScratch t_small = {nullptr, nullptr};
 static WsOff make_ws(const oard_config* c, const TopoDev& td) {
     const RDims d(c->hidden, c->num_radial);
     const size_t N = td.N, E = td.E + 1, A = td.A + 1;   // + the spare row of the padding columns
@@ -335,14 +319,11 @@ static WsOff make_ws(const oard_config* c, const TopoDev& td) {
     w.ew = take(E * d.WP * 4); w.mbuf = take(std::max(E, (size_t)(td.CI + td.CX) + 1) * d.HP * 4);
     w.xmsg = take(A * d.HP * 4); w.vmsg = take(A * 3 * d.HP * 4);
     w.dpos = take(N * 3 * 4); w.hout = take(N * 16 * 4);
-    // scratch of the stage-split latency edge kernels: only topologies small enough to ever take that path (the launch-shape
-    // thresholds are run-time options, so the launch re-checks that the buffers exist)
     w.al_rows = take(A * 4); w.al_src = take(A * 4); w.al_pre = take(A * 4); w.al_cnt = take((size_t)cdiv((long long)td.A, 256) * 4 + 4); w.al_n = take(4);
     w.d1s = take((size_t)cdiv((long long)td.A, 128) * 8 * d.D1T * 1024);
-    w.small_a = w.small_b = 0;
-    if (E <= (size_t)OARD_SMALL_MAX_EDGES) {
-        w.small_a = take(A * d.D1P * 4);
-    }
+    // scratch of the stage-split latency edge kernels: only topologies small enough to ever take that path (the launch-shape
+    // thresholds are run-time options, so the plan is told whether the buffer exists)
+    w.small_a = E <= (size_t)OARD_SMALL_MAX_EDGES ? take(A * d.D1P * 4) : 0;
     w.total = cur;
     return w;
 }
@@ -363,13 +344,6 @@ int set_lds(K kernel, size_t bytes) {
     ScopedLaunch sl_(fam, stream); if (!((g_skip_families >> (fam)) & 1)) \
     hipLaunchKernelGGL(kern, dim3((unsigned)(grid)), dim3(block), lds, stream, __VA_ARGS__); } while (0)
 
-#define GCL_CASE(id, WV_, GP_) case id: { \
-        LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, WV_, GP_, S1, S3, false>), cdiv(r1 - r0, 16 * WV_), WV_ * 64, \
-                   (GclStream<D, GP_>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
-// the throughput shape: 8 waves x 16 edges, two waves per SIMD, three LDS slabs (barrier inside the phase)
-#define GCL_RING3(TRAIN_, tape_) do { \
-        LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 8, 2, S1, S3, TRAIN_, false, 2, 3>), cdiv(r1 - r0, 16 * 8), 8 * 64, \
-                   (GclStream<D, 2>::LDS_BYTES / 2 * 3), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, tape_); return OARD_OK; } while (0)
 static int device_cus() {
     static int cus[64] = {};
     int d = 0;
@@ -382,181 +356,96 @@ static int device_cus() {
     }
     return cus[d];
 }
-// does an inference launch over `cols` columns take the streamed fp32 throughput shape - the 8-wave tile kernel or the persistent one
-// (launch_gcl_v1s decides the same way; forward_impl asks for every launch of a call before it lets the edge kernels sum the messages)
-static bool gcl_v1_throughput(int prec, int variant, int conc, long long cols) {
-    if (variant == 2 && cdiv(cols, 16) * conc <= 1024LL * g_auto_small) variant = 3;
-    if ((variant == 2 || variant == 3) && cdiv(cols, 16) * conc <= 512LL * g_auto_tiny) variant = 6;
-    return variant == 2 && !(prec & OARD_PREC_GCL_BF16X3);
-}
+// what every GCL edge launch of one layer shares (`mbuf`: one message row per edge, or msum - FwdPlan::msum)
+struct GclArgs {
+    const TopoDev& tp; const float* wb; const LayerOff& lo;
+    const float *stream, *P, *Q, *u0, *c0; float *ew_in, *ew_out, *mbuf;      // (the first-generation kernel updates ew_in in place)
+    GclTape tape; hipStream_t st;
+};
+// one launch of the plan.  (Every LAUNCH_LDS names its kernel: the attribute latch is per call site, so one site must launch one kernel.)
 template <class D, bool S1, bool S3>
-int launch_gcl_v1s(int prec, int variant, int conc, const TopoDev& tp, const float* wb, const LayerOff& lo, const float* stream, const float* P, const float* Q, const float* u0,
-                   const float* c0, long long r0, long long r1, const float* ew_in, float* ew_out, float* mbuf, const GclTape* tape, hipStream_t st,
-                   bool msum = false) {
-    if (r1 <= r0) return OARD_OK;
-    if (msum && (tape || !gcl_v1_throughput(prec, variant, conc, r1 - r0))) return OARD_EINVAL;      // (forward_impl asked the same function)
-    if (tape && (prec & OARD_PREC_TRAIN_BF16X3)) {    // training-mode forward in split precision (optional)
-        LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_b3<D, S1, S3, true>), cdiv(r1 - r0, 16 * 8), 8 * 64, (GclB3Stream<D>::LDS_BYTES), st, tp,
-                   wb + lo.gcl_b3, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, *tape);
-        return OARD_OK;
-    }
-    if (tape) {                  // training-mode forward: one shape (8 waves x 16 edges), pre-activations stored
-#ifdef OARD_EXPERIMENTS
-        if (variant == 7) {
-            LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 8, 2, S1, S3, true>), cdiv(r1 - r0, 16 * 8), 8 * 64,
-                       (GclStream<D, 2>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, *tape);
+int launch_gcl_v1s(const GclLaunch& L, bool msum, const GclArgs& a) {
+    constexpr size_t RING3 = GclStream<D, 2>::LDS_BYTES / 2 * 3;      // three LDS slabs (barrier inside the phase)
+#define GCL_STREAMED(kern, waves, lds, w_) do { LAUNCH_LDS(F_GCL_EDGE, kern, L.grid, (waves) * 64, lds, a.st, a.tp, w_, a.P, a.Q, a.u0, a.c0, \
+                                                           L.r0, L.r1, a.ew_in, a.ew_out, a.mbuf, a.tape); return OARD_OK; } while (0)
+    switch ((int)L.shape) {
+        case GCL_PERSIST:
+            if (msum) GCL_STREAMED((k_gcl_edge_p<D, S1, S3, false, true>), 8, RING3, a.stream);
+            GCL_STREAMED((k_gcl_edge_p<D, S1, S3>), 8, RING3, a.stream);
+        case GCL_RING3:
+            if (msum) GCL_STREAMED((k_gcl_edge_v1<D, 8, 2, S1, S3, false, true, 2, 3>), 8, RING3, a.stream);
+            GCL_STREAMED((k_gcl_edge_v1<D, 8, 2, S1, S3, false, false, 2, 3>), 8, RING3, a.stream);
+        case GCL_TRAIN_PERSIST: GCL_STREAMED((k_gcl_edge_p<D, S1, S3, true>), 8, RING3, a.stream);
+        case GCL_TRAIN_RING3: GCL_STREAMED((k_gcl_edge_v1<D, 8, 2, S1, S3, true, false, 2, 3>), 8, RING3, a.stream);
+        case GCL_B3: GCL_STREAMED((k_gcl_edge_b3<D, S1, S3>), 8, (GclB3Stream<D>::LDS_BYTES), a.wb + a.lo.gcl_b3);
+        case GCL_TRAIN_B3: GCL_STREAMED((k_gcl_edge_b3<D, S1, S3, true>), 8, (GclB3Stream<D>::LDS_BYTES), a.wb + a.lo.gcl_b3);
+        case GCL_W4: GCL_STREAMED((k_gcl_edge_v1<D, 4, 2, S1, S3, false>), 4, (GclStream<D, 2>::LDS_BYTES), a.stream);
+        case GCL_SMALL:
+            LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_small<D, 8, S1, S3>), L.grid, 512, (GclSmall<D>::LDS_BYTES), a.st,
+                       a.tp, a.wb, a.lo, a.P, a.Q, a.u0, a.c0, L.r0, L.r1, a.ew_out, a.mbuf);
             return OARD_OK;
-        }
-#endif
-        if (g_gcl_persist) {     // the training-mode forward is one sub-batch: persistent workgroups, balanced last round (oard_edge_p.h)
-            const long long nhalf = cdiv(cdiv(r1 - r0, 16), 4);
-            const long long want = g_gcl_grid > 0 ? g_gcl_grid : (g_gcl_grid < 0 ? cdiv(nhalf, 2LL * -g_gcl_grid) : device_cus());
-            LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_p<D, S1, S3, true>), std::min(nhalf, want), 8 * 64, (GclStream<D, 2>::LDS_BYTES / 2 * 3), st,
-                       tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, *tape);
-            return OARD_OK;
-        }
-        GCL_RING3(true, *tape);
-    }
-    if (variant == 2 && cdiv(r1 - r0, 16) * conc <= 1024LL * g_auto_small) variant = 3;
-    if ((variant == 2 || variant == 3) && cdiv(r1 - r0, 16) * conc <= 512LL * g_auto_tiny) variant = 6;
-    if (variant == 6) {          // latency kernel: 8 waves share 16 edges
-        LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_small<D, 8, S1, S3>), cdiv(r1 - r0, 16), 512, (GclSmall<D>::LDS_BYTES), st,
-                   tp, wb, lo, P, Q, u0, c0, r0, r1, ew_out, mbuf);
-        return OARD_OK;
-    }
-    switch (variant) {
-        case 2:
-            if (prec & OARD_PREC_GCL_BF16X3) {
-                LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_b3<D, S1, S3>), cdiv(r1 - r0, 16 * 8), 8 * 64, (GclB3Stream<D>::LDS_BYTES), st, tp,
-                           wb + lo.gcl_b3, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{});
-                return OARD_OK;
-            }
-            // A launch that has the chip to itself runs as persistent workgroups over half-tiles (oard_edge_p.h; same arithmetic, bit-identical
-            // rows): its last round is balanced (isolated 9.01 -> 8.62 ms per B = 64 step).  Concurrent sub-batches keep one tile per workgroup:
-            // there the other streams' kernels fill the tail, and workgroups that hold a CU for several tiles make THEM wait (measured:
-            // 17.93 ms per step with tiles, 18.05 - 18.3 with 64 ... 256 persistent workgroups per launch; gcl_persist = 2 forces it).
-            if (g_gcl_persist > 1 || (g_gcl_persist == 1 && conc == 1)) {
-                const long long nhalf = cdiv(cdiv(r1 - r0, 16), 4);
-                // gcl_grid < 0: -k = k rounds (128-row tiles) per workgroup
-                const long long want = g_gcl_grid > 0 ? g_gcl_grid : (g_gcl_grid < 0 ? cdiv(nhalf, 2LL * -g_gcl_grid) : (conc > 1 ? std::max(1, device_cus() / 2) : device_cus()));
-                if (msum) {
-                    LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_p<D, S1, S3, false, true>), std::min(nhalf, want), 8 * 64, (GclStream<D, 2>::LDS_BYTES / 2 * 3), st,
-                               tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{});
-                    return OARD_OK;
-                }
-                LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_p<D, S1, S3>), std::min(nhalf, want), 8 * 64, (GclStream<D, 2>::LDS_BYTES / 2 * 3), st,
-                           tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{});
-                return OARD_OK;
-            }
-            if (msum) {
-                LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 8, 2, S1, S3, false, true, 2, 3>), cdiv(r1 - r0, 16 * 8), 8 * 64,
-                           (GclStream<D, 2>::LDS_BYTES / 2 * 3), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{});
-                return OARD_OK;
-            }
-            GCL_RING3(false, GclTape{});
-        GCL_CASE(3, 4, 2)      // 4 waves x 16 edges (two workgroups per CU): small launches
-#ifdef OARD_EXPERIMENTS        // A/B shapes, only in experiment builds (tools/ab_gcl.sh)
-        GCL_CASE(7, 8, 2)      // the throughput shape with two slabs (barrier at the phase start; round 1 / 2)
-        case 4: {              // flag pipeline: no workgroup barriers, ring of 4 slabs (oard_edge_fp.h)
-            LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_fp<D, 8, 2, S1, S3, false>), cdiv(r1 - r0, 16 * 8), 8 * 64,
-                       (GclRing<D, 2, 4>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
-        case 5: {              // the same with a ring of 3 slabs (waves 0..3 at most one phase ahead)
-            LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_fp<D, 8, 2, S1, S3, false, 3>), cdiv(r1 - r0, 16 * 8), 8 * 64,
-                       (GclRing<D, 2, 3>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
-        GCL_CASE(8, 8, 3)
-        GCL_CASE(9, 8, 4)
-        case 10: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 12, 1, S1, S3, false, false, 3>), cdiv(r1 - r0, 16 * 12), 12 * 64,
-                              (GclStream<D, 1>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
-        case 11: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 12, 2, S1, S3, false, false, 3>), cdiv(r1 - r0, 16 * 12), 12 * 64,
-                              (GclStream<D, 2>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
-        case 12: { LAUNCH_LDS(F_GCL_EDGE, (k_gcl_edge_v1<D, 4, 1, S1, S3, false, false, 3>), cdiv(r1 - r0, 16 * 4), 4 * 64,
-                              (GclStream<D, 1>::LDS_BYTES), st, tp, stream, P, Q, u0, c0, r0, r1, ew_in, ew_out, mbuf, GclTape{}); return OARD_OK; }
+#ifdef OARD_EXPERIMENTS        // first generation; A/B shapes (tools/ab_gcl.sh)
+        case GCL_V0: LAUNCH(F_GCL_EDGE, (k_gcl_edge<D>), L.grid, 256, a.st, a.tp, a.wb, a.lo, a.P, a.Q, a.ew_in, a.mbuf); return OARD_OK;
+        case GCL_X0 + 7: GCL_STREAMED((k_gcl_edge_v1<D, 8, 2, S1, S3, false>), 8, (GclStream<D, 2>::LDS_BYTES), a.stream);      // two slabs (round 1 / 2)
+        case GCL_X0 + 8: GCL_STREAMED((k_gcl_edge_v1<D, 8, 3, S1, S3, false>), 8, (GclStream<D, 3>::LDS_BYTES), a.stream);
+        case GCL_X0 + 9: GCL_STREAMED((k_gcl_edge_v1<D, 8, 4, S1, S3, false>), 8, (GclStream<D, 4>::LDS_BYTES), a.stream);
+        // flag pipeline: no workgroup barriers, ring of 4 / 3 slabs (oard_edge_fp.h)
+        case GCL_X0 + 4: GCL_STREAMED((k_gcl_edge_fp<D, 8, 2, S1, S3, false>), 8, (GclRing<D, 2, 4>::LDS_BYTES), a.stream);
+        case GCL_X0 + 5: GCL_STREAMED((k_gcl_edge_fp<D, 8, 2, S1, S3, false, 3>), 8, (GclRing<D, 2, 3>::LDS_BYTES), a.stream);
+        case GCL_X0 + 10: GCL_STREAMED((k_gcl_edge_v1<D, 12, 1, S1, S3, false, false, 3>), 12, (GclStream<D, 1>::LDS_BYTES), a.stream);
+        case GCL_X0 + 11: GCL_STREAMED((k_gcl_edge_v1<D, 12, 2, S1, S3, false, false, 3>), 12, (GclStream<D, 2>::LDS_BYTES), a.stream);
+        case GCL_X0 + 12: GCL_STREAMED((k_gcl_edge_v1<D, 4, 1, S1, S3, false, false, 3>), 4, (GclStream<D, 1>::LDS_BYTES), a.stream);
 #endif
         default: return OARD_EINVAL;
     }
+#undef GCL_STREAMED
 }
-// one GCL edge pass of layer l: inner edges always run every stage; inter-object edges skip S1 in the first
-// layer (constant initial state) and S3 in the last (their updated state is never read)
+// one GCL edge pass of a layer: the one or two launches the plan lists for its kind
 template <class D>
-int launch_gcl_v1(int prec, int variant, int conc, const TopoDev& tp, const float* wb, const LayerOff& lo, const float* stream, const float* P, const float* Q, const float* u0,
-                  const float* c0, bool first, bool last, const float* ew_in, float* ew_out, float* mbuf, const GclTape* tape, hipStream_t st,
-                  bool msum = false) {
-    const long long A = tp.A, E = tp.E;
-    int rc;
-    const bool skip = g_gcl_skip || tape;
-    if (msum) {
-        // the edge kernels sum the messages per node: every layer runs the inner and the inter-object columns of the source-major list
-        // (TopoDev::col_info), `mbuf` is msum
-        const long long c_in = tp.CI, c_all = tp.CI + tp.CX;
-        const bool s1 = !(skip && first), s3 = !(skip && last);
-        // (where both lists run every stage they are ONE launch: the inter-object list starts on a multiple of 16 columns, so the wave tiles
-        // - and with them every partial sum - are the same as in two launches)
-        if (s1 && s3) return launch_gcl_v1s<D, true, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, 0, c_all, ew_in, ew_out, mbuf, tape, st, true);
-        rc = launch_gcl_v1s<D, true, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, 0, c_in, ew_in, ew_out, mbuf, tape, st, true);
+int launch_gcl_v1(const GclLayer& g, bool msum, const GclArgs& a) {
+    for (int i = 0; i < g.n; ++i) {
+        const GclLaunch& L = g.l[i];
+        const int rc = L.s1 ? (L.s3 ? launch_gcl_v1s<D, true, true>(L, msum, a) : launch_gcl_v1s<D, true, false>(L, msum, a))
+                            : (L.s3 ? launch_gcl_v1s<D, false, true>(L, msum, a) : launch_gcl_v1s<D, false, false>(L, msum, a));
         if (rc != OARD_OK) return rc;
-        if (s1) return launch_gcl_v1s<D, true, false>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, c_in, c_all, ew_in, ew_out, mbuf, tape, st, true);
-        if (s3) return launch_gcl_v1s<D, false, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, c_in, c_all, ew_in, ew_out, mbuf, tape, st, true);
-        return launch_gcl_v1s<D, false, false>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, c_in, c_all, ew_in, ew_out, mbuf, tape, st, true);
     }
-    if (!skip || (!first && !last)) return launch_gcl_v1s<D, true, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, 0, E, ew_in, ew_out, mbuf, tape, st);
-    rc = launch_gcl_v1s<D, true, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, 0, A, ew_in, ew_out, mbuf, tape, st);
-    if (rc != OARD_OK) return rc;
-    if (first && last) return launch_gcl_v1s<D, false, false>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, A, E, ew_in, ew_out, mbuf, tape, st);
-    if (first) return launch_gcl_v1s<D, false, true>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, A, E, ew_in, ew_out, mbuf, tape, st);
-    return launch_gcl_v1s<D, true, false>(prec, variant, conc, tp, wb, lo, stream, P, Q, u0, c0, A, E, ew_in, ew_out, mbuf, tape, st);
+    return OARD_OK;
 }
-// the EquiMessage edge kernel an inference launch of this size runs: 2 / 1 = the streamed fp32 kernel in its 8- / 4-wave shape, 4 = a
-// latency kernel, 5 = the split-precision kernel (launch_equi_v1 dispatches on it; forward_impl asks it whether layer 0 may leave out
-// the middle third of q, which only the 8-wave streamed kernel does)
-static int equi_v1_shape(int prec, int variant, int conc, long long A, const float* d1s) {
-    if (variant == 2 && cdiv(A, 16) * conc <= 512LL * g_auto_small) variant = 1;
-    if ((variant == 2 || variant == 1) && cdiv(A, 16) * conc <= 512LL * g_auto_tiny) variant = 4;
-    if (variant == 2 && (prec & OARD_PREC_EQUI_BF16X3) && d1s) variant = 5;
-    return variant;
-}
-#define EQUI_CASE(id, WV_, SKIP_) case id: { \
-        LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, WV_, false>), cdiv(tp.A, 16 * WV_), WV_ * 64, (EquiStream<D>::LDS_BYTES), st, \
-                   tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al, SKIP_); return OARD_OK; }
-// skip_mid: layer 0 of an inference forward whose node stage is the layer-0 form of k_equi_node_v1 (forward_impl: l0_skip) - the 8-wave
-// streamed kernel leaves out the middle third of q; every other kernel ignores it
+// the EquiMessage edge pass of layer l.  (The throughput kernels of both precisions take the list `al`; the latency kernels run every
+// inner row.  Under FwdPlan::l0_skip the 8-wave streamed kernel leaves out the middle third of q in layer 0.)
 template <class D>
-int launch_equi_v1(int prec, int variant, int conc, const TopoDev& tp, const float* wb, const LayerOff& lo, const float* stream, const float* dp0b, const float* ew,
-                   const float* rbuf, float* qbuf, float* zd1, float* cd, hipStream_t st, float* d1s = nullptr, ActList al = ActList{}, bool skip_mid = false) {
-    // (the latency kernels run every inner row: their q is zero on the rows outside the cutoff, which the node stage does not read when
-    // it walks the list; the throughput kernels of both precisions take the list)
-    if (zd1 && (prec & OARD_PREC_TRAIN_BF16X3) && d1s) {      // training-mode forward in split precision (optional)
-        LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_b3<D, true>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiB3Stream<D>::LDS_BYTES), st, tp, wb + lo.equi_b3,
-                   dp0b, wb + lo.dp2b, ew, rbuf, qbuf, d1s, zd1, cd, ActList{});
-        return OARD_OK;
-    }
-    if (zd1) {                   // training-mode forward
-        LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 8, true>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiStream<D>::LDS_BYTES), st,
-                   tp, stream, dp0b, ew, rbuf, qbuf, zd1, cd, ActList{}, 0);
-        return OARD_OK;
-    }
-    variant = equi_v1_shape(prec, variant, conc, tp.A, d1s);
-    if (skip_mid && variant != 2) return OARD_EINVAL;        // (forward_impl asked the same function)
-    if (variant == 4) {          // latency kernel: 8 waves share 16 edges
-        if (t_small.a && cdiv(tp.A, 16) * conc <= g_small_split) {   // stage-split latency path: 2 launches, few tiles only
-            const long long tiles = cdiv(tp.A, 16);
-            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_small_s1<D, 8>), tiles * cdiv(D::D1T, 8), 512, (size_t)D::WB * 1024, st,
-                       tp, wb, lo, ew, t_small.a);
-            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_small_s2<D, 8>), tiles * cdiv(3 * D::HT, 8), 512, (size_t)(D::D1T + D::RB) * 1024, st,
-                       tp, wb, lo, (const float*)t_small.a, rbuf, qbuf);
+int launch_equi_v1(const FwdPlan& plan, int l, const TopoDev& tp, const float* wb, const LayerOff& lo, const float* stream, const float* dp0b,
+                   const float* ew, const float* rbuf, float* qbuf, float* zd1, float* cd, hipStream_t st, float* d1s, float* small, ActList al) {
+    const long long tiles = cdiv(tp.A, 16);
+    switch (plan.equi) {
+        case EQ_TRAIN_B3:
+            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_b3<D, true>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiB3Stream<D>::LDS_BYTES), st, tp, wb + lo.equi_b3,
+                       dp0b, wb + lo.dp2b, ew, rbuf, qbuf, d1s, zd1, cd, ActList{});
             return OARD_OK;
-        }
-        LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_small<D, 8>), cdiv(tp.A, 16), 512, (EquiSmall<D>::LDS_BYTES), st,
-                   tp, wb, lo, ew, rbuf, qbuf);
-        return OARD_OK;
-    }
-    if (variant == 5) {          // split precision (oard_edge_b3.h): the throughput shape only
-        LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_b3<D>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiB3Stream<D>::LDS_BYTES), st, tp, wb + lo.equi_b3,
-                   dp0b, wb + lo.dp2b, ew, rbuf, qbuf, d1s, nullptr, nullptr, al);
-        return OARD_OK;
-    }
-    switch (variant) {
-        EQUI_CASE(1, 4, 0)
-        EQUI_CASE(2, 8, skip_mid ? 1 : 0)
+        case EQ_TRAIN:
+            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 8, true>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiStream<D>::LDS_BYTES), st,
+                       tp, stream, dp0b, ew, rbuf, qbuf, zd1, cd, ActList{}, 0);
+            return OARD_OK;
+        case EQ_SMALL_SPLIT:     // stage-split latency path: 2 launches, few tiles only
+            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_small_s1<D, 8>), tiles * cdiv(D::D1T, 8), 512, (size_t)D::WB * 1024, st, tp, wb, lo, ew, small);
+            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_small_s2<D, 8>), tiles * cdiv(3 * D::HT, 8), 512, (size_t)(D::D1T + D::RB) * 1024, st,
+                       tp, wb, lo, (const float*)small, rbuf, qbuf);
+            return OARD_OK;
+        case EQ_SMALL:           // latency kernel: 8 waves share 16 edges
+            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_small<D, 8>), tiles, 512, (EquiSmall<D>::LDS_BYTES), st, tp, wb, lo, ew, rbuf, qbuf);
+            return OARD_OK;
+        case EQ_B3:              // split precision (oard_edge_b3.h): the throughput shape only
+            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_b3<D>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiB3Stream<D>::LDS_BYTES), st, tp, wb + lo.equi_b3,
+                       dp0b, wb + lo.dp2b, ew, rbuf, qbuf, d1s, nullptr, nullptr, al);
+            return OARD_OK;
+        case EQ_W4:
+            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 4, false>), cdiv(tp.A, 16 * 4), 4 * 64, (EquiStream<D>::LDS_BYTES), st,
+                       tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al, 0);
+            return OARD_OK;
+        case EQ_W8:
+            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 8, false>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiStream<D>::LDS_BYTES), st,
+                       tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al, plan.l0_skip && l == 0 ? 1 : 0);
+            return OARD_OK;
         default: return OARD_EINVAL;
     }
 }
@@ -596,9 +485,10 @@ static TapeOff make_tape(const oard_config* c, const TopoDev& td) {
 
 // `tape` != NULL: training-mode forward (TapeOff layout): every layer's input edge state lives in its own tape
 // buffer (the update is out of place), the edge kernels store their pre-activations, and the node state at the
-// layer boundaries is written straight into its tape slots (no copies).  One launch shape, layer-0 / last-layer shortcuts always on.
+// layer boundaries is written straight into its tape slots (no copies).  Every launch shape comes from the plan (oard_plan.h), made here
+// once from the caller's copy of the options.
 template <class D>
-static int forward_impl(const oard_config* c, const TopoPart* topo, const float* wb, const float* const* xh,
+static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoPart* topo, const float* wb, const float* const* xh,
                         const float* t, int t_scalar, const float* cond, float* const* out, char* ws, char* tape,
                         int* status, hipStream_t st) {
     const TopoDev& tp = topo->d;
@@ -620,7 +510,6 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
     float* geo = slot(w.geo, to.geo); double* d64 = (double*)(ws + w.d64); float* rbuf = slot(w.rbuf, to.rbuf);
     float* mbuf = (float*)(ws + w.mbuf); float* xmsg = (float*)(ws + w.xmsg);
     float* vmsg = (float*)(ws + w.vmsg); float* dpos = (float*)(ws + w.dpos); float* hout = (float*)(ws + w.hout);
-    t_small = (w.small_a && !train) ? SmallScratch{(float*)(ws + w.small_a), (float*)(ws + w.small_b)} : SmallScratch{nullptr, nullptr};
     // edge state entering layer l (inference: one buffer updated in place)
     auto ew_at = [&](int l) -> float* { return train ? (float*)(tape + to.ew[l]) : (float*)(ws + w.ew); };
     float* ew = ew_at(0);
@@ -634,15 +523,13 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
         op.xh[k] = xh[k]; op.out[k] = out[k]; op.node_nf[k] = c->node_nf[k]; op.enc[k] = po.enc[k]; op.dec[k] = po.dec[k];
     }
     const long long N = tp.N, E = tp.E, A = tp.A;
-    const unsigned gN = (unsigned)cdiv(N, 64), gE = (unsigned)cdiv(E, 64), gA = (unsigned)cdiv(A, 64);
+    const unsigned gN = (unsigned)cdiv(N, 64), gA = (unsigned)cdiv(A, 64);
     const double cutoff = (double)c->cutoff;
-    const int gcl_variant = train ? 2 : g_gcl_variant, equi_variant = train ? 2 : g_equi_variant;
-    const int node_variant = train ? 1 : g_node_variant;
-    const bool gcl_skip = train || g_gcl_skip;
+    const FwdPlan plan = make_fwd_plan({opt, c->precision, train, topo->conc, tp.npb, device_cus(), A, E, tp.CI, tp.CX, c->num_layers, w.small_a != 0});
+    const bool msum = plan.msum, use_al = plan.use_al, nv1 = plan.node != NODE_V0;
     const int stop_after = train ? 0 : g_stop_after;
-    // the inner rows inside the cutoff, compacted per call: EquiMessage (edge kernel and node-side gather) runs those only.  Inference with
-    // the streamed edge kernels and the v1 node stages; the training-mode forward tapes every row for its backward pass.
-    const bool use_al = !train && g_equi_skip && A > 0 && equi_variant != 0 && node_variant == 1;
+    // the inner rows inside the cutoff, compacted per call (plan.use_al): inference with the streamed edge kernels and the v1 node stages;
+    // the training-mode forward tapes every row for its backward pass
     int* al_cnt = (int*)(ws + w.al_cnt);
     const ActList al = use_al ? ActList{(const int*)(ws + w.al_rows), (const int*)(ws + w.al_src), (const int*)(ws + w.al_pre), (const int*)(ws + w.al_n)}
                               : ActList{nullptr, nullptr, nullptr, nullptr};
@@ -654,7 +541,7 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
     LAUNCH(F_INIT, k_geom, tp.n_groups, 64, st, tp, (const float*)pos, cutoff, pf64, pf32, x1, pp0, labels);
     // inter-object rows start as the constant row; with the layer-0 shortcut nobody reads them before layer 0
     // writes them, so they are only materialised for the unspecialised paths and for the debug tap
-    if (!(gcl_skip && gcl_variant != 0) || stop_after == 1)
+    if (plan.fill_edges || stop_after == 1)
         LAUNCH(F_INIT, k_fill_edges, std::min<long long>(cdiv((E - A + 1) * (D::WP / 4), 256), 8192), 256, st,
                wb + po.c0row, ew + (size_t)A * D::WP, E - A + 1, D::WP);
     if (A > 0) {
@@ -669,32 +556,23 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
     // exactly one tile of each H-wide layer
     constexpr int NW = D::HT <= 16 ? D::HT : 8;
     const unsigned gNb = (unsigned)cdiv(N, tp.npb);
-    if (node_variant >= 1) {
+    if (plan.init_v1) {
         LAUNCH(F_INIT, (k_neighbor_v1<D, NW>), gNb, NW * 64, st, tp, wb, po, (const float*)zemb, (const float*)nb, (const float*)ew, s_at(0), s1);
         LAUNCH(F_INIT, (k_s2v_agg_v1<D, NW>), gNb, NW * 64, st, tp, (const float*)s1, (const float*)ew, (const float*)geo, ne1);
     } else if constexpr (kV0) {
         LAUNCH(F_INIT, (k_neighbor<D>), gN, 256, st, tp, wb, po, (const float*)zemb, (const float*)nb, (const float*)ew, s_at(0), s1);
         LAUNCH(F_INIT, (k_s2v_agg<D>), gN, 256, st, tp, (const float*)s1, (const float*)ew, (const float*)geo, ne1);
     } else return OARD_EINVAL;
-    // small launches: one workgroup per (64 edges, hidden tile) instead of per 64 edges
-    if (A > 0) LAUNCH2(F_INIT, (k_scalarize<D>), gA, (gA * topo->conc <= 2048 ? D::HT : 1), 256, st, tp, wb, po, (const float*)ne1, (const float*)geo, ew);
+    if (A > 0) LAUNCH2(F_INIT, (k_scalarize<D>), gA, (plan.scalarize_tiles ? D::HT : 1), 256, st, tp, wb, po, (const float*)ne1, (const float*)geo, ew);
     HIP_TRY(hipMemsetAsync(vec, 0, (size_t)N * 3 * D::HP * sizeof(float), st));
     if (stop_after == 1) return OARD_OK;
 
     float* vec2 = (float*)(ws + w.vec2);
     float* vcur = vec;          // holds the current vec; v1 ping-pongs between vec and vec2
     float* vnext = vec2;
-    // GCL messages summed per node inside the edge kernels (st_msum) and ~6 partial rows per node gathered instead of one row per edge:
-    // decided once per call and sub-batch, both kernels or neither - only if EVERY GCL launch of the call takes the streamed fp32
-    // throughput shape (8-wave tile or persistent kernel) and the node stage is the large-batch one.  The training-mode forward tapes agg
-    // and keeps the message rows.
-    const bool msum = !train && g_gcl_msum && E > 0 && gcl_variant == 2 && node_variant == 1 && equi_variant != 0 && tp.npb > 4 &&
-                      (tp.CI == 0 || gcl_v1_throughput(c->precision, gcl_variant, topo->conc, tp.CI)) &&
-                      (tp.CX == 0 || gcl_v1_throughput(c->precision, gcl_variant, topo->conc, tp.CX));      // (the smaller launches decide)
-    g_gcl_msum_taken = msum;
+    g_gcl_msum_taken = msum;    // (`mbuf` then holds the per-node partial sums, and the training-mode forward never takes it: it tapes agg)
     for (int l = 0; l < c->num_layers; ++l) {
         const LayerOff lo = po.layer[l];
-        const bool nv1 = node_variant == 1 && equi_variant != 0;
         const unsigned gN16 = (unsigned)cdiv(N, tp.npb);
         float* ew_in = ew_at(l);
         float* ew_out = ew_at(l + 1);
@@ -703,19 +581,11 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
         if (nv1) LAUNCH(F_NODE, (k_node_pre_v1<D, NW>), gN16, NW * 64, st, tp, wb, po, lo, (const float*)s_at(l), (const float*)pp0, xhb, P, Q);
         else if constexpr (kV0) LAUNCH(F_NODE, (k_node_pre<D>), gN, 256, st, tp, wb, po, lo, (const float*)s, (const float*)pp0, xhb, P, Q);
         else return OARD_EINVAL;
-        if (E > 0) {
-            if (gcl_variant == 0) {
-                if constexpr (kV0) LAUNCH(F_GCL_EDGE, (k_gcl_edge<D>), gE, 256, st, tp, wb, lo, (const float*)P, (const float*)Q, ew_in, mbuf);
-                else return OARD_EINVAL;
-            } else {
-                GclTape gt{};
-                if (train) gt = GclTape{(float*)(tape + to.z1[l]), (float*)(tape + to.z2[l]), (float*)(tape + to.att[l]), (float*)(tape + to.z3[l])};
-                int rc = launch_gcl_v1<D>(c->precision, gcl_variant, topo->conc, tp, wb, lo, wb + lo.gcl_stream, P, Q, wb + po.u0, wb + po.c0row, l == 0,
-                                          l == c->num_layers - 1, ew_in, ew_out, mbuf, train ? &gt : nullptr, st, msum);
-                if (rc != OARD_OK) return rc;
-            }
-        }
-        const bool rows = tp.npb <= 4;                       // small batches: gathers walk the rows with the wave's columns (row_lanes)
+        GclTape gt{};
+        if (train) gt = GclTape{(float*)(tape + to.z1[l]), (float*)(tape + to.z2[l]), (float*)(tape + to.att[l]), (float*)(tape + to.z3[l])};
+        int rc = launch_gcl_v1<D>(plan.gcl_at(l), msum, GclArgs{tp, wb, lo, wb + lo.gcl_stream, P, Q, wb + po.u0, wb + po.c0row, ew_in, ew_out, mbuf, gt, st});
+        if (rc != OARD_OK) return rc;
+        const bool rows = plan.node == NODE_ROWS;            // small batches: gathers walk the rows with the wave's columns (row_lanes)
         if (nv1 && rows) LAUNCH(F_NODE, (k_gcl_node_v1<D, NW, true>), gN16, NW * 64, st, tp, wb, lo, (const float*)xhb, (const float*)mbuf, s_mid_at(l), xq,
                                 train ? (float*)(tape + to.agg[l]) : nullptr);
         else if (nv1 && msum) LAUNCH(F_NODE, (k_gcl_node_v1<D, NW, false, true>), gN16, NW * 64, st, tp, wb, lo, (const float*)xhb, (const float*)mbuf, s_mid_at(l), xq,
@@ -725,7 +595,7 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
         else if constexpr (kV0) LAUNCH(F_NODE, (k_gcl_node<D>), gN, 256, st, tp, wb, lo, (const float*)xhb, (const float*)mbuf, s, xq);
         else return OARD_EINVAL;
         if (stop_after == 100 + 10 * l + 1) { topo->vec_final = (size_t)((char*)vcur - ws); return OARD_OK; }
-        if (equi_variant == 0) {
+        if (plan.equi == EQ_V0) {
             if constexpr (kV0) {
                 if (A > 0) LAUNCH(F_EQUI_EDGE, (k_equi_edge<D>), gA, 256, st, tp, wb, lo, (const float*)ew_out, (const float*)rbuf,
                                   (const float*)geo, (const float*)xq, (const float*)vcur, xmsg, vmsg);
@@ -733,16 +603,12 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
                        s, vcur, v2buf, scal, vdot);
             } else return OARD_EINVAL;
         } else {
-            // layer 0 of an inference forward: vec is exactly zero there, so the third of q that only multiplies vec[src] is neither computed
-            // (8-wave streamed fp32 edge kernel) nor gathered (large-batch node stage) - both or neither, the node stage must not read what
-            // the edge kernel did not write.  The training-mode forward tapes that third of dir_proj's output for the backward pass.
-            const bool l0_skip = l == 0 && !train && g_equi_l0_skip && A > 0 && nv1 && !rows &&
-                                 equi_v1_shape(c->precision, equi_variant, topo->conc, A, (const float*)(ws + w.d1s)) == 2;
+            const bool l0_skip = l == 0 && plan.l0_skip;       // edge kernel and node stage both leave out the third of q that multiplies vec = 0
             if (l == 0) g_equi_l0_taken = l0_skip;
             if (A > 0) {
-                int rc = launch_equi_v1<D>(c->precision, equi_variant, topo->conc, tp, wb, lo, wb + lo.equi_stream, wb + lo.dp0b, ew_out, rbuf, vmsg,
-                                           train ? (float*)(tape + to.zd1[l]) : nullptr, train ? (float*)(tape + to.cd[l]) : nullptr, st,
-                                           (float*)(ws + w.d1s), al, l0_skip);
+                rc = launch_equi_v1<D>(plan, l, tp, wb, lo, wb + lo.equi_stream, wb + lo.dp0b, ew_out, rbuf, vmsg,
+                                       train ? (float*)(tape + to.zd1[l]) : nullptr, train ? (float*)(tape + to.cd[l]) : nullptr, st,
+                                       (float*)(ws + w.d1s), (float*)(ws + w.small_a), al);
                 if (rc != OARD_OK) return rc;
             }
 #define EQUI_NODE_V1(D_, ROWS_, XC_) LAUNCH(F_NODE, (k_equi_node_v1<D_, NW, ROWS_, XC_>), gN16, NW * 64, st, tp, wb, lo, (const float*)vmsg, \
@@ -789,7 +655,7 @@ static int forward_impl(const oard_config* c, const TopoPart* topo, const float*
         add(to.geo, (size_t)A, GEO_STRIDE); add(to.rbuf, (size_t)A, D::RP);
         if (z.count > 0) LAUNCH(F_OTHER, k_zero_rows, z.count, 256, st, z);
     }
-    if (node_variant >= 1)
+    if (plan.init_v1)
         LAUNCH(F_NODE, (k_out_v1<D, NW>), gNb, NW * 64, st, tp, wb, po, (const float*)s_at(c->num_layers), (const float*)vcur, dpos, hout, status);
     else if constexpr (kV0)
         LAUNCH(F_NODE, (k_out<D>), gN, 256, st, tp, wb, po, (const float*)s, (const float*)vcur, dpos, hout, status);
@@ -1608,11 +1474,12 @@ int oard_forward(const oard_config* c, const oard_topology* topo, const void* pa
     // sub-batches run concurrently on the topology's side streams (sequentially when timing / debugging)
     const bool concurrent = topo->n_parts > 1 && !g_timing.on && g_stop_after == 0 && !g_sequential;
     if (concurrent) HIP_TRY(hipEventRecord(topo->ev_fork, st));
+    const FwdOptions opt = g_fwd;       // one set of rules for every sub-batch of this call
     for (int p = 0; p < topo->n_parts; ++p) {
         hipStream_t sp = (concurrent && p > 0) ? topo->side[p] : st;
         if (concurrent && p > 0) HIP_TRY(hipStreamWaitEvent(sp, topo->ev_fork, 0));
         int rc = OARD_EINVAL;
-        DISPATCH_DIMS(c, rc = forward_impl<D>(c, &topo->parts[p], (const float*)packed, xh, t, t_is_scalar, cond, out,
+        DISPATCH_DIMS(c, rc = forward_impl<D>(opt, c, &topo->parts[p], (const float*)packed, xh, t, t_is_scalar, cond, out,
                                               (char*)ws + topo->parts[p].ws_off, nullptr, (int*)status, sp));
         if (rc != OARD_OK) return rc;
         if (concurrent && p > 0) HIP_TRY(hipEventRecord(topo->ev_join[p], sp));
@@ -1750,7 +1617,7 @@ int oard_forward_train(const oard_config* c, const oard_topology* topo, const vo
         HIP_TRY(hipMemsetAsync(tape, 0xFF, make_tape(c, topo->parts[0].d).total, st));
     }
     int rc = OARD_EINVAL;
-    DISPATCH_DIMS(c, rc = forward_impl<D>(c, &topo->parts[0], (const float*)packed, xh, t, t_is_scalar, cond, out,
+    DISPATCH_DIMS(c, rc = forward_impl<D>(FwdOptions(g_fwd), c, &topo->parts[0], (const float*)packed, xh, t, t_is_scalar, cond, out,
                                           (char*)ws + topo->parts[0].ws_off, (char*)tape, (int*)status, st));
     return rc;
 }
@@ -2407,35 +2274,24 @@ int oard_tap(const oard_config* c, const oard_topology* topo, const void* ws_, i
 int oard_debug_stop_after(int code) { g_stop_after = code; return OARD_OK; }
 int oard_debug_option(const char* name, int value) {
     if (!name) return OARD_EINVAL;
-    if (!kV0 && value == 0 && (strcmp(name, "gcl_variant") == 0 || strcmp(name, "equi_variant") == 0 || strcmp(name, "node_variant") == 0))
-        return OARD_EINVAL;                      // the first-generation kernels exist in experiment builds only
-    if (strcmp(name, "gcl_variant") == 0) { g_gcl_variant = value; return OARD_OK; }
-    if (strcmp(name, "equi_variant") == 0) { g_equi_variant = value; return OARD_OK; }
-    if (strcmp(name, "node_variant") == 0) { g_node_variant = value; return OARD_OK; }
+    static const struct { const char* name; int* value; } table[] = {
+        {"gcl_variant", &g_fwd.gcl_variant}, {"equi_variant", &g_fwd.equi_variant}, {"node_variant", &g_fwd.node_variant},
+        {"auto_small", &g_fwd.auto_small}, {"auto_tiny", &g_fwd.auto_tiny}, {"small_split", &g_fwd.small_split},
+        {"gcl_persist", &g_fwd.gcl_persist}, {"gcl_grid", &g_fwd.gcl_grid}, {"gcl_skip", &g_fwd.gcl_skip}, {"equi_skip", &g_fwd.equi_skip},
+        {"equi_l0_skip", &g_fwd.equi_l0_skip}, {"gcl_msum", &g_fwd.gcl_msum},
+        {"skip_families", &g_skip_families}, {"parts", &g_parts}, {"sequential", &g_sequential}, {"poison", &g_poison}, {"npb", &g_npb},
+        {"wgrad_wgs", &g_wgrad_wgs}, {"wgrad_t16", &g_wgrad_t16}, {"wgrad_queue", &g_wgrad_queue}, {"gate_fold", &g_gate_fold},
+        {"wgrad_lds", &g_wgrad_lds}, {"wgrad_shapes", &g_wgrad_shapes}, {"train_dual", &g_train_dual}};
     if (strcmp(name, "experiments") == 0) return kV0 ? OARD_OK : OARD_EINVAL;      // query: is this an experiment build?
-    if (strcmp(name, "gcl_skip") == 0) { g_gcl_skip = value; return OARD_OK; }
-    if (strcmp(name, "equi_skip") == 0) { g_equi_skip = value; return OARD_OK; }
-    if (strcmp(name, "equi_l0_skip") == 0) { g_equi_l0_skip = value; return OARD_OK; }
-    if (strcmp(name, "gcl_msum") == 0) { g_gcl_msum = value; return OARD_OK; }
     if (strcmp(name, "gcl_msum_taken") == 0) return g_gcl_msum_taken ? OARD_OK : OARD_EINVAL;      // query: did the last forward take that form?
     if (strcmp(name, "equi_l0_taken") == 0) return g_equi_l0_taken ? OARD_OK : OARD_EINVAL;      // query: did the last forward skip it?
-    if (strcmp(name, "gcl_persist") == 0) { g_gcl_persist = value; return OARD_OK; }
-    if (strcmp(name, "gcl_grid") == 0) { g_gcl_grid = value; return OARD_OK; }
-    if (strcmp(name, "skip_families") == 0) { g_skip_families = value; return OARD_OK; }
-    if (strcmp(name, "parts") == 0) { g_parts = value; return OARD_OK; }
-    if (strcmp(name, "sequential") == 0) { g_sequential = value; return OARD_OK; }
-    if (strcmp(name, "poison") == 0) { g_poison = value; return OARD_OK; }
-    if (strcmp(name, "auto_small") == 0) { g_auto_small = value; return OARD_OK; }
-    if (strcmp(name, "auto_tiny") == 0) { g_auto_tiny = value; return OARD_OK; }
-    if (strcmp(name, "npb") == 0) { g_npb = value; return OARD_OK; }
-    if (strcmp(name, "wgrad_wgs") == 0) { g_wgrad_wgs = value; return OARD_OK; }
-    if (strcmp(name, "wgrad_t16") == 0) { g_wgrad_t16 = value; return OARD_OK; }
-    if (strcmp(name, "wgrad_queue") == 0) { g_wgrad_queue = value; return OARD_OK; }
-    if (strcmp(name, "gate_fold") == 0) { g_gate_fold = value; return OARD_OK; }
-    if (strcmp(name, "wgrad_lds") == 0) { g_wgrad_lds = value; return OARD_OK; }
-    if (strcmp(name, "wgrad_shapes") == 0) { g_wgrad_shapes = value & 3; return OARD_OK; }
-    if (strcmp(name, "train_dual") == 0) { g_train_dual = value; return OARD_OK; }
-    if (strcmp(name, "small_split") == 0) { g_small_split = value; return OARD_OK; }
+    for (const auto& e : table) {
+        if (strcmp(name, e.name) != 0) continue;
+        // the first-generation kernels (variant 0) exist in experiment builds only
+        if (!kV0 && value == 0 && strstr(name, "_variant")) return OARD_EINVAL;
+        *e.value = e.value == &g_wgrad_shapes ? value & 3 : value;
+        return OARD_OK;
+    }
     return OARD_EINVAL;
 }
 #ifdef OARD_PHASE_PROBE

@@ -155,5 +155,5 @@ struct WsOff {
         geo, d64, rbuf, ew, mbuf, xmsg, vmsg, dpos, hout, total;   // xmsg..vmsg double as qbuf [A][3][HP] (v1)
     size_t al_rows, al_src, al_pre, al_cnt, al_n;   // ActList of this call + the per-block counts it is built from
     size_t d1s;                    // split-precision EquiMessage kernel: SiLU(d1) in wave-tile order, [ceil(A / 128) * 8][D1T][256] floats
-    size_t small_a, small_b;       // stage-split EquiMessage latency path: d1 [A+1][D1P]; 0 = not allocated (large topologies)
+    size_t small_a;                // stage-split EquiMessage latency path: d1 [A+1][D1P]; 0 = not allocated (large topologies)
 };
