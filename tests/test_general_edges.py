@@ -2,7 +2,9 @@
 edge lists that are not the complete graph per sample - what the reference accepts (dynamics/egnn_dynamics.py:63-72), builds with
 `edge_cutoff` (utils/_graph_tools.py:31-33) and exercises in its own model tests (tests/model/test_equiv.py:177-230,
 tests/model/test_subgraphs.py:285-339).  Gate: 1e-5 of the reference evaluated in float64 (fixtures g11_* made from the reference by
-oracle/make_goldens.py; larger graphs against the oracle on the box, which the fixtures pin to 3e-16 on general graphs)."""
+oracle/make_goldens.py; graphs off the fixtures against the float64 oracle evaluated in the test, which the fixtures pin to 3e-16 on general
+graphs: random lists of a few hundred edges, cut batches up to 9 384 edges, and one reaction of 3 x 86 atoms at 66 306 and 66 006 edges,
+where every edge-level dense layer runs the two-row-tile kernel - tests/test_general_dense.py holds that kernel alone to its own gate)."""
 import pytest
 import torch
 
@@ -250,3 +252,114 @@ def test_forced_general_path_builds_no_production_tables(name):
         rv, rh = c.split(c.ref64)
         print(f"{name} forced general: vel {rel(v, rv):.2e} h {rel(h, rh):.2e}")
         assert rel(v, rv) <= TOL and rel(h, rh) <= TOL
+
+
+# ---- from 65 536 edges on: HipExec::gemm gives every edge-level dense layer to k_general_gemm_f64<2> (two row tiles per wave) -----------------
+class _BigReaction:
+    """One reaction of 3 x 86 atoms at production widths, two layers (with one, the vec-mixing third of EquiMessage's outputs multiplies
+    vec = 0 and reaches no output): N = 258.  `complete`: E = 66 306, E % 32 = 2 - the last workgroup's second row tile is empty; forced
+    onto the general path.  `dropped`: 300 edges fewer (seeded, kept order), E = 66 006, E % 32 = 22 - a partial second tile; not complete,
+    so it takes the general path by itself.  Node-level layers (258 and 774 rows) stay on one row tile.  The float64 oracle (literal node
+    frame; about 12 s and 5.5 GB of host memory per list) is evaluated once per list."""
+
+    def __init__(self):
+        from oareactdiff_amd.spec import PRODUCTION_LEFTNET_CONFIG, state_spec, synthetic_state_dict
+        from test_hip_parity import _random_case
+        self.cfg = dict(PRODUCTION_LEFTNET_CONFIG, num_layers=2)
+        self.sd = synthetic_state_dict(state_spec(self.cfg, [9, 9, 9], 1), self.cfg, seed=7)
+        self.xh, ei, self.t, self.cond, self.nfs, self.cm = _random_case([86], 2.0, 31, self.cfg)
+        keep = torch.ones(ei.shape[1], dtype=torch.bool)
+        keep[torch.randperm(ei.shape[1], generator=torch.Generator().manual_seed(32))[:300]] = False
+        self.ei = {"complete": ei, "dropped": ei[:, keep]}
+        self._ref = {}
+
+    def dyn(self, dev, path):
+        from oareactdiff_amd.dynamics import EGNNDynamics
+        d = EGNNDynamics(model_config=dict(self.cfg), fragment_names=["R", "TS", "P"], node_nfs=[9, 9, 9], edge_nf=0, condition_nf=1, device=dev)
+        d.load_state_dict(self.sd, strict=True)
+        d.edge_list_path = path
+        return d
+
+    def args(self, which, dev):
+        return ([x.to(dev) for x in self.xh], self.ei[which].to(dev), self.t.to(dev), self.cond.to(dev), self.nfs.to(dev), self.cm.to(dev))
+
+    def ref(self, which):
+        if which not in self._ref:
+            out = oracle.dynamics_forward({k: v.double() for k, v in self.sd.items()}, self.cfg, [x.double() for x in self.xh], self.ei[which],
+                                          self.t.double(), self.cond.double(), self.nfs, self.cm, 1, nodeframe="literal")
+            self._ref[which] = self.split(out)
+        return self._ref[which]
+
+    @staticmethod
+    def split(outs):
+        return (torch.cat([o[:, :3].detach().cpu().double().reshape(-1) for o in outs]),
+                torch.cat([o[:, 3:].detach().cpu().double().reshape(-1) for o in outs]))
+
+
+@pytest.fixture(scope="module")
+def big_reaction():
+    return _BigReaction()
+
+
+@pytest.mark.parametrize("which", ["complete", "dropped"])
+def test_network_on_two_row_tiles_per_wave(big_reaction, which, monkeypatch):
+    """The whole network where the edge-level dense layers run k_general_gemm_f64<2>: matrix pipe against plain threads (they differ in the
+    order of a float64 sum only), against the float64 oracle, and - the complete list - against the production kernels."""
+    dev = torch.device("cuda:0")
+    B = big_reaction
+    E = B.ei[which].shape[1]
+    assert E >= 65536 and E % 32 not in (0, 16) and E == {"complete": 66306, "dropped": 66006}[which]
+    path = "general" if which == "complete" else "auto"
+    outs = {}
+    for how in ("matrix", "threads"):
+        monkeypatch.setenv("OARD_GENERAL_GEMM", how)                       # read by the library on every call
+        dyn = B.dyn(dev, path)
+        with torch.no_grad():
+            out, _ = dyn(*B.args(which, dev))
+        assert dyn._last_topo.graph is not None
+        if which == "dropped":
+            assert dyn._last_topo.handle is None                               # not complete: nothing forced it here
+            assert _capi_is_complete(dyn) == 0
+        outs[how] = B.split(out)
+    (va, ha), (vb, hb) = outs["matrix"], outs["threads"]
+    rv, rh = B.ref(which)
+    print(f"{which}: E {E}  matrix pipe vs threads vel {rel(va, vb):.2e} h {rel(ha, hb):.2e}; matrix vs f64 oracle vel {rel(va, rv):.2e} "
+          f"h {rel(ha, rh):.2e}; threads vs f64 oracle vel {rel(vb, rv):.2e} h {rel(hb, rh):.2e}")
+    assert rel(va, vb) <= 2e-7 and rel(ha, hb) <= 2e-7
+    assert rel(va, rv) <= TOL and rel(ha, rh) <= TOL
+    if which == "complete":
+        prod = B.dyn(dev, "auto")
+        with torch.no_grad():
+            out, _ = prod(*B.args(which, dev))
+        assert prod._last_topo.handle is not None and prod._last_topo.graph is None
+        vp, hp = B.split(out)
+        print(f"{which}: general vs production kernels vel {rel(va, vp):.2e} h {rel(ha, hp):.2e}")
+        assert rel(va, vp) <= TOL and rel(ha, hp) <= TOL
+
+
+def _capi_is_complete(dyn):
+    from oareactdiff_amd import _capi
+    return int(_capi.lib().oard_graph_is_complete(dyn._last_topo.graph))
+
+
+@pytest.mark.parametrize("which", ["g11_arbitrary", "dropped"])
+def test_general_path_does_not_depend_on_what_the_workspace_holds(big_reaction, which):
+    """The caller owns the workspace and its contents are arbitrary (include/oard.h): the host executor's harness poisons it
+    (tests/general_host/harness.cpp); here the module's own workspace tensor is filled with 0xFF bytes (NaN patterns, pointers to nowhere)
+    between two calls, which must agree bit for bit - on a small fixture and on the 66 006-edge list."""
+    dev = torch.device("cuda:0")
+    if which == "dropped":
+        dyn, args = big_reaction.dyn(dev, "auto"), big_reaction.args(which, dev)
+    else:
+        c = Case(which)
+        dyn, args = _dyn(c, dev), _args(c, dev)
+    with torch.no_grad():
+        a, _ = dyn(*args)
+        assert dyn._last_topo.graph is not None and dyn._last_topo.handle is None
+        ws = dyn._call_buffers.ws                                              # the tensor _call_buffers.workspace(...) handed out
+        assert ws is not None and ws.dtype == torch.uint8 and ws.numel() > 0
+        ws.fill_(0xFF)
+        b, _ = dyn(*args)
+        assert dyn._call_buffers.ws is ws
+    assert all(bool(torch.isfinite(x).all()) for x in a)
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
