@@ -167,6 +167,36 @@ int oard_sampler_step_dev(const oard_config* cfg, const oard_topology* topo, int
                           const float* const* h0_dev, const float* coef_dev, int zero_feature_noise,
                           float* const* out_dev, oard_stream_t stream);
 
+/* ---- fused RePaint step (next row N3) -----------------------------------------------------------
+ * One step of EnVariationalDiffusion.inpaint's loop (oa_reactdiff/diffusion/en_diffusion.py:788-853) in ONE launch per
+ * sub-batch: one wavefront per (sample, object) group.  Per object k, rows in the reference's order; eps(n) is the noise n with
+ * its position columns made CoM-free per group and its feature columns 0 if zero_feature_noise:
+ *   k in fixed:     y = a_s * xfix + sigma_s * eps(noise_known)                                  (q(z_s | x), :803-805)
+ *   k not fixed:    y = z / alpha_ts - eps_hat * c_eps + sigma * eps(noise_step) ;  y_pos -= mean_group(y_pos)      (:806-815)
+ *   h0_dev[k] != NULL:  the feature columns of y := h0                                           (:817-825)
+ *   jump != 0:      out = a_j * y + sigma_j * eps(noise_jump) ;  out_pos -= mean_group(out_pos)  (no h0 override; :848)
+ *   else:           out = y
+ * coef = [a_s, sigma_s, alpha_ts, c_eps, sigma, jump, a_j, sigma_j]; bit k of fixed_mask set = object k is fixed.
+ * Every group sum (the CoM of each noise draw, of the un-projected update, of the jump result) is a float64 sum in a fixed order
+ * (lane-strided partials, then a fixed 64-lane reduction), removed in float64: a projected block keeps a mean of at most
+ * 2^-24 max|out| whatever the operands' offset, and a group's result does not depend on the sub-batch split.
+ * Operands of objects that do not use them may be NULL (z / eps_hat / noise_step of a fixed object, xfix / noise_known of a
+ * free one; the arrays themselves when no object needs them).  noise_jump_dev may be NULL only here and only with jump == 0.
+ * out_dev[k] must not be one of object k's operands (OARD_EINVAL): the kernel reads whole groups while it writes rows. */
+int oard_inpaint_step(const oard_config* cfg, const oard_topology* topo, unsigned int fixed_mask,
+                      const float* const* z_dev, const float* const* eps_hat_dev, const float* const* xfix_dev,
+                      const float* const* noise_known_dev, const float* const* noise_step_dev,
+                      const float* const* noise_jump_dev, const float* const* h0_dev, const float coef[8],
+                      int zero_feature_noise, float* const* out_dev, oard_stream_t stream);
+
+/* As oard_inpaint_step with the eight scalars read from device memory (coef_dev[8]), the jump flag among them (a wave-uniform
+ * branch): ONE captured launch serves the steps that jump and those that do not.  noise_jump_dev is required. */
+int oard_inpaint_step_dev(const oard_config* cfg, const oard_topology* topo, unsigned int fixed_mask,
+                          const float* const* z_dev, const float* const* eps_hat_dev, const float* const* xfix_dev,
+                          const float* const* noise_known_dev, const float* const* noise_step_dev,
+                          const float* const* noise_jump_dev, const float* const* h0_dev, const float* coef_dev,
+                          int zero_feature_noise, float* const* out_dev, oard_stream_t stream);
+
 /* ---- introspection (tests / profiling) --------------------------------------------------------
  * Copies an intermediate tensor of the LAST oard_forward on this workspace into dst_dev, in the
  * reference's node / edge order, dense [rows, cols] fp32.  `which`: see OARD_TAP_*.  `layer`

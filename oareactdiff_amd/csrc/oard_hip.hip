@@ -1533,6 +1533,72 @@ static int sampler_step_impl(const oard_config* c, const oard_topology* topo, in
     return OARD_OK;
 }
 
+// One k_inpaint_step launch per sub-batch on the caller's stream, one wavefront per (sample, object) group.  `hc`: the host scalars
+// (coef == NULL) - the device row otherwise.
+static int inpaint_step_impl(const oard_config* c, const oard_topology* topo, unsigned fixed_mask, const float* const* z,
+                             const float* const* eh, const float* const* xfix, const float* const* nk, const float* const* ns,
+                             const float* const* nj, const float* const* h0, InpaintCoef hc, const float* coef,
+                             int zero_feature_noise, float* const* out, oard_stream_t stream) {
+    if (!config_ok(c) || !topo || !out) return OARD_EINVAL;
+    if (c->n_obj != topo->n_obj) return OARD_EINVAL;
+    const unsigned all = c->n_obj >= 32 ? ~0u : (1u << c->n_obj) - 1u;
+    if (fixed_mask & ~all) return OARD_EINVAL;
+    const bool any_fixed = (fixed_mask & all) != 0, any_free = (fixed_mask & all) != all;
+    if (any_fixed && (!xfix || !nk)) return OARD_EINVAL;
+    if (any_free && (!z || !eh || !ns)) return OARD_EINVAL;
+    if (!nj && (coef != nullptr || hc.jump != 0.f)) return OARD_EINVAL;      // the device row may ask for a jump at any replay
+    InpaintPtrs ip;
+    memset(&ip, 0, sizeof(ip));
+    for (int k = 0; k < c->n_obj; ++k) {
+        const bool fx = (fixed_mask >> k) & 1u;
+        ip.z[k] = z ? z[k] : nullptr;
+        ip.eh[k] = eh ? eh[k] : nullptr;
+        ip.xfix[k] = xfix ? xfix[k] : nullptr;
+        ip.nk[k] = nk ? nk[k] : nullptr;
+        ip.ns[k] = ns ? ns[k] : nullptr;
+        ip.nj[k] = nj ? nj[k] : nullptr;
+        ip.h0[k] = h0 ? h0[k] : nullptr;
+        ip.out[k] = out[k];
+        ip.node_nf[k] = c->node_nf[k];
+        if (topo->obj_start[k + 1] == topo->obj_start[k]) continue;      // an object without rows: its pointers are never read
+        if (!out[k]) return OARD_EINVAL;
+        if (fx ? (!ip.xfix[k] || !ip.nk[k]) : (!ip.z[k] || !ip.eh[k] || !ip.ns[k])) return OARD_EINVAL;
+        if ((nj || coef) && !ip.nj[k]) return OARD_EINVAL;
+        // the kernel reads whole groups while it writes rows: no operand may be the output
+        const float* o = out[k];
+        if (o == ip.z[k] || o == ip.eh[k] || o == ip.xfix[k] || o == ip.nk[k] || o == ip.ns[k] || o == ip.nj[k] || o == ip.h0[k])
+            return OARD_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int p = 0; p < topo->n_parts; ++p)
+        if (topo->parts[p].d.n_groups > 0)
+            LAUNCH(F_OTHER, k_inpaint_step, topo->parts[p].d.n_groups, 64, st, topo->parts[p].d, ip, fixed_mask, hc, coef,
+                   zero_feature_noise);
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+int oard_inpaint_step(const oard_config* c, const oard_topology* topo, unsigned fixed_mask, const float* const* z,
+                      const float* const* eh, const float* const* xfix, const float* const* noise_known,
+                      const float* const* noise_step, const float* const* noise_jump, const float* const* h0, const float coef[8],
+                      int zero_feature_noise, float* const* out, oard_stream_t stream) {
+    topo_touch(topo, (hipStream_t)stream);
+    if (!coef) return OARD_EINVAL;
+    const InpaintCoef hc = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7]};
+    return inpaint_step_impl(c, topo, fixed_mask, z, eh, xfix, noise_known, noise_step, noise_jump, h0, hc, nullptr,
+                             zero_feature_noise, out, stream);
+}
+
+int oard_inpaint_step_dev(const oard_config* c, const oard_topology* topo, unsigned fixed_mask, const float* const* z,
+                          const float* const* eh, const float* const* xfix, const float* const* noise_known,
+                          const float* const* noise_step, const float* const* noise_jump, const float* const* h0,
+                          const float* coef_dev, int zero_feature_noise, float* const* out, oard_stream_t stream) {
+    topo_touch(topo, (hipStream_t)stream);
+    if (!coef_dev) return OARD_EINVAL;
+    return inpaint_step_impl(c, topo, fixed_mask, z, eh, xfix, noise_known, noise_step, noise_jump, h0, InpaintCoef{}, coef_dev,
+                             zero_feature_noise, out, stream);
+}
+
 // ------------------------------------------------------------------------------------------------
 // training: tape, training-mode forward, backward of the edge stages, weight-gradient GEMM
 // ------------------------------------------------------------------------------------------------

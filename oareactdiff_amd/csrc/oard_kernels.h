@@ -360,6 +360,116 @@ OARD_KERNEL __global__ void k_sampler_step(TopoDev tp, SamplerPtrs sp, int mode,
 }
 
 // =====================================================================================================
+// fused RePaint step (en_diffusion.py:788-853): one wavefront per (sample, object) group, group sums in float64
+// =====================================================================================================
+struct InpaintPtrs {
+    const float* z[OARD_MAX_OBJECTS];
+    const float* eh[OARD_MAX_OBJECTS];
+    const float* xfix[OARD_MAX_OBJECTS];
+    const float* nk[OARD_MAX_OBJECTS];      // noise of the known branch, of the denoising step, of the jump
+    const float* ns[OARD_MAX_OBJECTS];
+    const float* nj[OARD_MAX_OBJECTS];
+    const float* h0[OARD_MAX_OBJECTS];
+    float* out[OARD_MAX_OBJECTS];
+    int node_nf[OARD_MAX_OBJECTS];
+};
+struct InpaintCoef { float a_s, sigma_s, alpha_ts, c_eps, sigma, jump, a_j, sigma_j; };
+
+// every lane gets the same bits: at each step the two partners add the same pair
+OARD_DEV double wave_sum_f64(double v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// What k_sampler_step needs up to five launches for (mode 3 | mode 0 + projection, then mode 4 + projection on a jump step), per group:
+//   fixed object:  y = a_s xfix + sigma_s eps(nk)            else:  y = z / alpha_ts - eh c_eps + sigma eps(ns);  y_pos -= mean(y_pos)
+//   h0 != NULL:    features of y := h0
+//   jump:          out = a_j y + sigma_j eps(nj);  out_pos -= mean(out_pos)          else: out = y
+// Lanes stride over the group's rows; every mean is a float64 sum (lane partials in ascending rows, then wave_sum_f64) of float32
+// values, removed in float64 and rounded once - so one projection leaves 2^-24 max|out| and the result depends on the group alone.
+// Rows are recomputed per pass from the operands (at most 16 rows per lane, OARD_MAX_GROUP / 64): no scratch, no LDS.
+// coef != NULL: the eight scalars, the jump flag among them, come from device memory (one captured launch serves both kinds of step).
+OARD_KERNEL __global__ __launch_bounds__(64) void k_inpaint_step(TopoDev tp, InpaintPtrs ip, unsigned fixed_mask, InpaintCoef hc,
+                                                                 const float* __restrict__ coef, int zero_h) {
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int g0 = tp.grp_ptr[q], ng = tp.grp_ptr[q + 1] - g0;
+    if (ng <= 0) return;
+    InpaintCoef c = hc;
+    if (coef != nullptr) {
+        c.a_s = coef[0]; c.sigma_s = coef[1]; c.alpha_ts = coef[2]; c.c_eps = coef[3];
+        c.sigma = coef[4]; c.jump = coef[5]; c.a_j = coef[6]; c.sigma_j = coef[7];
+    }
+    const int obj = q % tp.n_obj, nf = ip.node_nf[obj];
+    const bool fixed = (fixed_mask >> obj) & 1u, jump = c.jump != 0.f;
+    const float* Z = fixed ? ip.xfix[obj] : ip.z[obj];
+    const float* E = ip.eh[obj];
+    const float* R = fixed ? ip.nk[obj] : ip.ns[obj];
+    const float* J = ip.nj[obj];
+    const float* H = ip.h0[obj];
+    float* O = ip.out[obj];
+    const double inv = 1.0 / (double)ng;
+    // un-projected first stage of one value (eps already CoM-free / zeroed).  The fused multiply-adds are spelled out: every pass
+    // recomputes its rows, and the mean a pass removes must be the mean of exactly the values the last pass forms.
+    auto first = [&](size_t o, float eps) -> float {
+        return fixed ? fmaf(c.sigma_s, eps, c.a_s * Z[o]) : fmaf(c.sigma, eps, fmaf(-E[o], c.c_eps, Z[o] / c.alpha_ts));
+    };
+    // ---- pass 1: CoM of the raw noise draws -----------------------------------------------------
+    double r0 = 0, r1 = 0, r2 = 0, j0 = 0, j1 = 0, j2 = 0;
+    for (int k = lane; k < ng; k += 64) {
+        const size_t o = (size_t)tp.node_row[g0 + k] * nf;
+        r0 += (double)R[o]; r1 += (double)R[o + 1]; r2 += (double)R[o + 2];
+        if (jump) { j0 += (double)J[o]; j1 += (double)J[o + 1]; j2 += (double)J[o + 2]; }
+    }
+    r0 = wave_sum_f64(r0) * inv; r1 = wave_sum_f64(r1) * inv; r2 = wave_sum_f64(r2) * inv;
+    if (jump) { j0 = wave_sum_f64(j0) * inv; j1 = wave_sum_f64(j1) * inv; j2 = wave_sum_f64(j2) * inv; }
+    // ---- pass 2: CoM of the un-projected denoising update (the known branch is not projected, :803-805) ----
+    double u0 = 0, u1 = 0, u2 = 0;
+    if (!fixed) {
+        for (int k = lane; k < ng; k += 64) {
+            const size_t o = (size_t)tp.node_row[g0 + k] * nf;
+            u0 += (double)first(o, (float)((double)R[o] - r0));
+            u1 += (double)first(o + 1, (float)((double)R[o + 1] - r1));
+            u2 += (double)first(o + 2, (float)((double)R[o + 2] - r2));
+        }
+        u0 = wave_sum_f64(u0) * inv; u1 = wave_sum_f64(u1) * inv; u2 = wave_sum_f64(u2) * inv;
+    }
+    // y of one position value, projected
+    auto ypos = [&](size_t o, double rm, double um) -> float {
+        const float u = first(o, (float)((double)R[o] - rm));
+        return fixed ? u : (float)((double)u - um);
+    };
+    auto jumped = [&](float y, float eps) -> float { return fmaf(c.sigma_j, eps, c.a_j * y); };
+    // ---- pass 3: CoM of the jump result -----------------------------------------------------------
+    double v0 = 0, v1 = 0, v2 = 0;
+    if (jump) {
+        for (int k = lane; k < ng; k += 64) {
+            const size_t o = (size_t)tp.node_row[g0 + k] * nf;
+            v0 += (double)jumped(ypos(o, r0, u0), (float)((double)J[o] - j0));
+            v1 += (double)jumped(ypos(o + 1, r1, u1), (float)((double)J[o + 1] - j1));
+            v2 += (double)jumped(ypos(o + 2, r2, u2), (float)((double)J[o + 2] - j2));
+        }
+        v0 = wave_sum_f64(v0) * inv; v1 = wave_sum_f64(v1) * inv; v2 = wave_sum_f64(v2) * inv;
+    }
+    // ---- pass 4: the rows ---------------------------------------------------------------------------
+    for (int k = lane; k < ng; k += 64) {
+        const size_t row = (size_t)tp.node_row[g0 + k], o = row * nf;
+        float y0 = ypos(o, r0, u0), y1 = ypos(o + 1, r1, u1), y2 = ypos(o + 2, r2, u2);
+        if (jump) {
+            y0 = (float)((double)jumped(y0, (float)((double)J[o] - j0)) - v0);
+            y1 = (float)((double)jumped(y1, (float)((double)J[o + 1] - j1)) - v1);
+            y2 = (float)((double)jumped(y2, (float)((double)J[o + 2] - j2)) - v2);
+        }
+        O[o] = y0; O[o + 1] = y1; O[o + 2] = y2;
+        for (int f = 3; f < nf; ++f) {
+            float y = H ? H[row * (size_t)(nf - 3) + (size_t)(f - 3)] : first(o + f, zero_h ? 0.f : R[o + f]);
+            if (jump) y = jumped(y, zero_h ? 0.f : J[o + f]);
+            O[o + f] = y;
+        }
+    }
+}
+
+// =====================================================================================================
 // geometry block in float64 (leftnet.py:747-761, 707-722, 812-834)
 // =====================================================================================================
 // one 64-thread block per (sample, object) group: cutoff graph inside the group, the reference's

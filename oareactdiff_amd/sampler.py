@@ -6,7 +6,10 @@
 (mu, CoM-free noise, CoM projection, pos_only feature reset fused; launched a second time as a bare projection after the steps
 that project, `_project_again`); the schedule scalars come from a host
 table, the NaN flag stays on the device, and the reference's four `.item()` asserts per step are gone, so
-the loop never synchronises the host with the GPU."""
+the loop never synchronises the host with the GPU.
+
+`DiffusionSampler.inpaint` (row N3) runs the RePaint loop the same way on the fused step kernel `oard_inpaint_step`: one launch per
+step for the known branch, the denoised branch and the forward jump, group sums in float64."""
 from __future__ import annotations
 
 import contextlib
@@ -19,7 +22,7 @@ from torch import Tensor
 from . import _capi
 from .dynamics import EGNNDynamics
 from .graph_tools import get_edges_index, get_mask_for_frag, get_n_frag_switch
-from .schedule import Schedule, get_repaint_schedule
+from .schedule import Schedule, get_repaint_schedule, repaint_steps
 
 
 class DiffusionSampler:
@@ -61,6 +64,8 @@ class DiffusionSampler:
         self.last_status: Optional[Tensor] = None
         #: upper bound on the pre-drawn noise of the hipGraph-replayed loop (`sample(graph=True)` / small batches)
         self.noise_block_bytes = 64 << 20
+        self.last_inpaint_loop: Optional[str] = None       # the loop the last `inpaint` took: "graphed", "fused" or "unfused"
+        self.last_inpaint_refills = 0                      # noise-table refills of the last graphed `inpaint`
 
     def _layout(self, fragments_nodes: List[Tensor], dev):
         """Batch-layout tensors (masks, combined_mask, edge_index, n_frag_switch) on the device, cached by the
@@ -139,8 +144,8 @@ class DiffusionSampler:
         removes carries ~1e-7 of the UN-projected values per row: when those share an offset far above their spread (|mean| ~ 60,
         spread ~ 1) a mean of 3e-6 ... 1e-5 max|out| stays in the output.  The second pass sums values of the size of the output
         and leaves 1e-8.  The loops' own operands are CoM-free, so for them the pass changes last bits only; it is here because the
-        wrappers promise a CoM-free result for ANY operands.  (The one-launch form - float64 group sums inside k_sampler_step -
-        belongs to a change that re-collects the profile passes, which are tied to the kernel sources: tests/test_docs_in_step.py.)"""
+        wrappers promise a CoM-free result for ANY operands.  (The one-launch form - float64 group sums inside the step kernel - is
+        what the inpainting loop's k_inpaint_step does; k_sampler_step and `sample` keep the two passes.)"""
         arr = _capi.ptr_array
         rc = _capi.lib().oard_sampler_step(C.byref(self.dynamics._config()), topo.handle, 4, arr(x), None, arr(x), arr(h0),
                                            C.c_float(1.0), C.c_float(0.0), C.c_float(0.0), 1 if self.pos_only else 0, arr(out), stream)
@@ -366,15 +371,112 @@ class DiffusionSampler:
                 out[0] = [torch.cat([g[1][k] for g in got], dim=0) for k in range(len(self.node_nfs))]
         return out, masks, (lo, hi)
 
+    def _inpaint_step(self, topo, fixed_mask, z, eh, xf, nk, ns, nj, h0, coef, out, stream):
+        """One launch of the fused RePaint step (`oard_inpaint_step`; include/oard.h has the formulas).  `coef`: the eight scalars
+        [a_s, sigma_s, alpha_ts, c_eps, sigma, jump, a_j, sigma_j] as host floats, or an [8] device tensor (the launch a hipGraph
+        replays: `oard_inpaint_step_dev`).  `nj` may be None for a host `coef` whose jump flag is 0."""
+        L = _capi.lib()
+        arr = _capi.ptr_array
+        head = (C.byref(self.dynamics._config()), topo.handle, fixed_mask, arr(z), arr(eh), arr(xf), arr(nk), arr(ns), arr(nj), arr(h0))
+        tail = (1 if self.pos_only else 0, arr(out), stream)
+        if isinstance(coef, Tensor):
+            _capi.check(L.oard_inpaint_step_dev(*head, coef.data_ptr(), *tail), "oard_inpaint_step_dev")
+        else:
+            _capi.check(L.oard_inpaint_step(*head, (C.c_float * 8)(*coef), *tail), "oard_inpaint_step")
+
+    def _repaint_coefficients(self, s: int, jump_to: Optional[int], timesteps: int) -> List[float]:
+        """The coefficient row of `oard_inpaint_step` for the step to s, re-noised to `jump_to` if that is set."""
+        a_s, sig_s = self.schedule.alpha_sigma(s, timesteps)
+        co = self.schedule.step(s, timesteps)
+        a_j, sig_j = self.schedule.forward_jump(s, jump_to, timesteps) if jump_to is not None else (1.0, 0.0)
+        return [a_s, sig_s, co.alpha_ts, co.c_eps, co.sigma, 0.0 if jump_to is None else 1.0, a_j, sig_j]
+
+    def _graphed_repaint(self, dyn, topo, timesteps, steps, fixed_mask, za, xf, draw, hsel, edge_index, conditions, n_frag_switch,
+                         combined_mask, dev):
+        """The RePaint steps of the fused `inpaint` loop as ONE captured hipGraph, replayed once per entry of `steps` - the protocol of
+        `_graphed_steps`: a side stream, one eager warm-up step, one capture, replays.  Per-step device tables indexed by a device-side
+        counter: t, the 8-float coefficient row (jump flag included: the kernel branches on it, so one launch serves both kinds of
+        step), the prior coefficient, and three noise tables (known / step / jump) refilled in blocks of at most
+        `noise_block_bytes` in the eager loop's draw order - a jump row is drawn only for the steps that jump, so a seeded run
+        consumes the generator exactly like the eager loop.  The graph holds [table lookups, oard_forward, the prior axpy,
+        oard_inpaint_step_dev, z <- z_new, counters += 1]: the eager loop's kernels on the eager loop's operands."""
+        n_obj = len(self.node_nfs)
+        n_steps = len(steps)
+        coef_tab = torch.tensor([self._repaint_coefficients(s, j, timesteps) for s, j in steps], dtype=torch.float32, device=dev)   # [S,8]
+        idx = torch.tensor([s + 1 for s, _ in steps], device=dev)
+        t_tab = (torch.arange(timesteps + 1, device=dev, dtype=torch.float32) / timesteps)[idx]      # the eager loop's t, bit for bit
+        prior_tab = self._prior_table(timesteps, dev)[idx] if self.prior_std is not None else None
+        per_step = 3 * 4 * sum(int(x.numel()) for x in za)
+        block = max(1, min(n_steps, self.noise_block_bytes // max(per_step, 1)))
+        tabs = [[torch.empty((block,) + tuple(x.shape), dtype=torch.float32, device=dev) for x in za] for _ in range(3)]   # known, step, jump
+        counter = torch.zeros(1, dtype=torch.long, device=dev)           # entry of `steps` (t / coefficient / prior tables)
+        slot = torch.zeros(1, dtype=torch.long, device=dev)              # row of the current block's noise tables
+        z = [x.clone() for x in za]
+        z_new = [torch.empty_like(x) for x in za]
+        self.last_inpaint_refills = 0
+
+        def refill(first, n_rows):
+            for r in range(n_rows):
+                for which in range(3 if steps[first + r][1] is not None else 2):
+                    d = draw()
+                    for k in range(n_obj):
+                        tabs[which][k][r].copy_(d[k])
+            slot.zero_()
+            self.last_inpaint_refills += 1
+
+        def one_step():
+            t_cur = t_tab.index_select(0, counter)
+            coef = coef_tab.index_select(0, counter).view(8)
+            nk, ns, nj = ([nt.index_select(0, slot)[0] for nt in tab] for tab in tabs)
+            eps_hat, _ = dyn(z, edge_index, t_cur, conditions, n_frag_switch, combined_mask)
+            if prior_tab is not None:
+                self._add_prior(eps_hat, z, prior_tab.index_select(0, counter))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self._inpaint_step(topo, fixed_mask, z, eps_hat, xf, nk, ns, nj, hsel, coef, z_new, stream)
+            for a, b in zip(z, z_new):
+                a.copy_(b)
+            counter.add_(1)
+            slot.add_(1)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                                    # eager warm-up on the capture stream (entry 0)
+            for tab in tabs:                                             # rows never drawn (no jump) are never read; keep them finite
+                for nt in tab:
+                    nt.zero_()
+            refill(0, min(block, n_steps))
+            one_step()
+            done, in_block = 1, 1
+            if n_steps > 1:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=side):
+                    one_step()
+                while done < n_steps:
+                    if in_block == block:
+                        refill(done, min(block, n_steps - done))
+                        in_block = 0
+                    g.replay()
+                    done += 1
+                    in_block += 1
+        torch.cuda.current_stream(dev).wait_stream(side)
+        return z
+
     @torch.no_grad()
     def inpaint(self, n_samples: int, fragments_nodes: List[Tensor], conditions: Optional[Tensor] = None,
                 return_frames: int = 1, resamplings: int = 1, jump_length: int = 1, timesteps: Optional[int] = None,
                 xh_fixed: Optional[List[Tensor]] = None, frag_fixed: Optional[List[int]] = None,
-                noise_fn: Optional[Callable[[int], List[Tensor]]] = None) -> Tuple[list, List[Tensor]]:
+                noise_fn: Optional[Callable[[int], List[Tensor]]] = None, fused: bool = True,
+                graph: Optional[bool] = None) -> Tuple[list, List[Tensor]]:
         """RePaint-style conditional generation, mirror of `EnVariationalDiffusion.inpaint`
         (en_diffusion.py:722-883): objects in `frag_fixed` follow q(z_s | x_fixed), the others are denoised,
         with `resamplings` x `jump_length` forward jumps.  Noise draws are consumed in the reference's order
-        (per step: known-branch noise, denoising noise, then the jump noise if any)."""
+        (per step: known-branch noise, denoising noise, then the jump noise if any).
+        `fused` (default): one `oard_inpaint_step` launch per RePaint step and sub-batch on two ping-ponged state lists (float64 group
+        sums, one projection).  `fused=False`: the earlier sequence of up to five `oard_sampler_step` launches per step, bit for bit as
+        before; the fused loop differs from it in last bits.
+        `graph=True`: replay the fused step as a captured hipGraph (`_graphed_repaint`, bit-identical to the fused eager loop; needs
+        `fused`, one returned frame and a stream that is not itself being captured).  None = the eager loop: unlike `sample`'s, this
+        replay measured SLOWER than the eager loop at 1, 8 and 64 reactions (profiles/inpaint_loop.txt), so nothing selects it
+        automatically.  `self.last_inpaint_loop` names the loop the call took: "graphed", "fused" or "unfused"."""
         timesteps = self.T if timesteps is None else timesteps
         assert 0 < return_frames <= timesteps and timesteps % return_frames == 0
         assert xh_fixed is not None and len(xh_fixed)
@@ -382,6 +484,8 @@ class DiffusionSampler:
         dyn = self.dynamics
         n_obj = len(self.node_nfs)
         pd = self.pos_dim
+        assert all(0 <= int(k) < n_obj for k in frag_fixed)
+        assert fused or not graph, "the hipGraph replay is built on the fused step"
         with self._run(n_samples, fragments_nodes, conditions) as (dev, layout, conditions, topo, stream):
             masks, combined_mask, edge_index, n_frag_switch = layout
             xf = [x.to(device=dev, dtype=torch.float32).clone() for x in xh_fixed]
@@ -404,7 +508,28 @@ class DiffusionSampler:
             self._step_kernel(topo, 2, None, None, draw(), hsel, 0.0, 0.0, 1.0, zt, stream)
             t_table = torch.arange(timesteps + 1, device=dev, dtype=torch.float32) / timesteps
             ptab = self._prior_table(timesteps, dev) if self.prior_std is not None else None
-            schedule = get_repaint_schedule(resamplings, jump_length, timesteps)
+            steps = repaint_steps(resamplings, jump_length, timesteps)
+            fixed_mask = sum(1 << k for k in set(int(k) for k in frag_fixed))
+            use_graph = fused and bool(graph)                  # None: the eager loop (measured faster at every batch size, see `graph`)
+            self.last_inpaint_loop = "graphed" if use_graph else "fused" if fused else "unfused"
+            if use_graph:
+                assert return_frames == 1, "intermediate frames need the eager loop"
+                zt = self._graphed_repaint(dyn, topo, timesteps, steps, fixed_mask, zt, xf, draw, hsel, edge_index, conditions,
+                                           n_frag_switch, combined_mask, dev)
+            elif fused:
+                spare = new()                                  # the two state lists of the whole loop, ping-ponged
+                for s, jump_to in steps:
+                    nk = draw()                                                                         # :797-805
+                    eps_hat, _ = dyn(zt, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
+                    if ptab is not None:
+                        self._add_prior(eps_hat, zt, ptab[s + 1: s + 2])
+                    ns = draw()
+                    nj = draw() if jump_to is not None else None                                        # :833-850
+                    self._inpaint_step(topo, fixed_mask, zt, eps_hat, xf, nk, ns, nj, hsel,
+                                       self._repaint_coefficients(s, jump_to, timesteps), spare, stream)
+                    zt, spare = spare, zt
+            # fused=False: the launch sequence from before the fused step, untouched (A/B); the fused loops above leave it nothing to do
+            schedule = [] if fused else get_repaint_schedule(resamplings, jump_length, timesteps)
             s = timesteps - 1
             for i, n_denoise in enumerate(schedule):
                 for j in range(n_denoise):
@@ -437,6 +562,37 @@ class DiffusionSampler:
         out_samples = [None] * return_frames
         out_samples[0] = self._to_samples(x, h0, h0_long=True)
         return out_samples, masks
+
+    @torch.no_grad()
+    def inpaint_sharded(self, fragments_nodes: List[Tensor], xh_fixed: List[Tensor], conditions: Optional[Tensor] = None,
+                        seed: int = 0, gather: bool = False, **kw):
+        """`inpaint` on a GLOBAL batch sharded over the ranks of the default process group, the mirror of `sample_sharded`: every rank
+        takes the reactions `shard_range(B, rank, world)` - their atom counts, conditions and the rows of every `xh_fixed[k]` (by the
+        cumulative atom counts of object k) -, seeds with `seed + rank` and runs `inpaint`; no collective inside the loop.
+        `gather=True`: one host-side gather of the samples on rank 0, in batch order.  Returns (samples, masks, (lo, hi))."""
+        import torch.distributed as dist
+        from .shard import shard_range
+        on = dist.is_available() and dist.is_initialized()
+        rank, world = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
+        B = int(fragments_nodes[0].numel())
+        lo, hi = shard_range(B, rank, world)
+        local = [f[lo:hi] for f in fragments_nodes]
+        cond = conditions[lo:hi] if conditions is not None else None
+        xl = []
+        for f, x in zip(fragments_nodes, xh_fixed):
+            off = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.long), f.cpu().long()]), 0)
+            xl.append(x[int(off[lo]): int(off[hi])])
+        torch.manual_seed(seed + rank)                     # seeds the device generators too
+        out, masks = self.inpaint(hi - lo, local, conditions=cond, xh_fixed=xl, **kw)
+        if gather and world > 1:
+            mine = (lo, [o.cpu() for o in out[0]])
+            got = [None] * world if rank == 0 else None
+            dist.gather_object(mine, got, dst=0)
+            if rank == 0:
+                got.sort(key=lambda t: t[0])
+                out = list(out)
+                out[0] = [torch.cat([g[1][k] for g in got], dim=0) for k in range(len(self.node_nfs))]
+        return out, masks, (lo, hi)
 
     def _unnormalize_z(self, z: List[Tensor]) -> List[Tensor]:
         nv, nb, pd = self.norm_values, self.norm_biases, self.pos_dim

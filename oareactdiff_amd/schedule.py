@@ -123,3 +123,19 @@ def get_repaint_schedule(resamplings: int, jump_length: int, timesteps: int):
                 out.append(residual)
             cur += residual
     return list(reversed(out))
+
+
+def repaint_steps(resamplings: int, jump_length: int, timesteps: int):
+    """The steps the nested loop of `inpaint` visits (en_diffusion.py:788-853), flat: [(s, jump_to or None), ...] - the step denoises
+    t = s + 1 -> s and, where `jump_to` is set, then re-noises s -> jump_to = s + jump_length (the last step of every block of the
+    RePaint schedule but the final one).  One network call per entry."""
+    schedule = get_repaint_schedule(resamplings, jump_length, timesteps)
+    out, s = [], timesteps - 1
+    for i, n_denoise in enumerate(schedule):
+        for j in range(n_denoise):
+            jump = j == n_denoise - 1 and i < len(schedule) - 1
+            out.append((s, s + jump_length if jump else None))
+            if jump:
+                s += jump_length
+            s -= 1
+    return out
