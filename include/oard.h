@@ -81,7 +81,12 @@ int oard_supported(const oard_config* cfg);
  * pointer of the i-th tensor in that canonical order (buffers included; unused tensors may be
  * NULL).  Packs every Linear into MFMA-fragment order (16x16 chunks) plus the
  * padded bias / LayerNorm vectors and the constant inter-object edge row.  Call again after
- * any weight update. */
+ * any weight update.
+ * The blob ends with room for one table per layer of EquiMessage's rbf_proj as a function of exp(-d) (csrc/oard_rbf_table.h;
+ * 3 * ceil(H / 16) * 2049 * 32 floats each, 10.2 MB at H = 196).  oard_pack_weights neither writes nor reads that part - a trainer
+ * packs after every update -; the first inference-mode oard_forward on the blob that can use the tables builds and checks them
+ * there on its stream and synchronises it once (a call being captured into a graph does not, and runs without them unless an
+ * earlier call built them).  Do not copy a blob in place of packing it: the library keeps the tables' state by the blob's address. */
 size_t oard_param_count(const oard_config* cfg);
 size_t oard_packed_bytes(const oard_config* cfg);
 int oard_pack_weights(const oard_config* cfg, const float* const* params_dev, size_t n_params,

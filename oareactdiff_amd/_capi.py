@@ -164,7 +164,7 @@ def lib() -> C.CDLL:
     L.oard_timing_reset.argtypes = []; L.oard_timing_reset.restype = C.c_int
     L.oard_timing_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(i64)]; L.oard_timing_get.restype = C.c_int
     for env, opt in (("OARD_GCL_VARIANT", b"gcl_variant"), ("OARD_EQUI_VARIANT", b"equi_variant"),
-                     ("OARD_NODE_VARIANT", b"node_variant"), ("OARD_GCL_SKIP", b"gcl_skip"), ("OARD_EQUI_SKIP", b"equi_skip"), ("OARD_EQUI_L0_SKIP", b"equi_l0_skip"), ("OARD_GCL_MSUM", b"gcl_msum"), ("OARD_GCL_PERSIST", b"gcl_persist"), ("OARD_GCL_GRID", b"gcl_grid"), ("OARD_PARTS", b"parts"), ("OARD_SEQUENTIAL", b"sequential"), ("OARD_POISON", b"poison"), ("OARD_AUTO_SMALL", b"auto_small"), ("OARD_AUTO_TINY", b"auto_tiny"), ("OARD_NPB", b"npb"),
+                     ("OARD_NODE_VARIANT", b"node_variant"), ("OARD_GCL_SKIP", b"gcl_skip"), ("OARD_EQUI_SKIP", b"equi_skip"), ("OARD_EQUI_L0_SKIP", b"equi_l0_skip"), ("OARD_EQUI_RBF_TABLE", b"equi_rbf_table"),("OARD_GCL_MSUM", b"gcl_msum"), ("OARD_GCL_PERSIST", b"gcl_persist"), ("OARD_GCL_GRID", b"gcl_grid"), ("OARD_PARTS", b"parts"), ("OARD_SEQUENTIAL", b"sequential"), ("OARD_POISON", b"poison"), ("OARD_AUTO_SMALL", b"auto_small"), ("OARD_AUTO_TINY", b"auto_tiny"), ("OARD_NPB", b"npb"),
                      ("OARD_WGRAD_WGS", b"wgrad_wgs"), ("OARD_WGRAD_LDS", b"wgrad_lds"), ("OARD_WGRAD_T16", b"wgrad_t16"), ("OARD_WGRAD_QUEUE", b"wgrad_queue"), ("OARD_GATE_FOLD", b"gate_fold"), ("OARD_WGRAD_SHAPES", b"wgrad_shapes"), ("OARD_TRAIN_DUAL", b"train_dual"), ("OARD_SMALL_SPLIT", b"small_split"),
                      ("OARD_SKIP_FAMILIES", b"skip_families")):
         if os.environ.get(env) not in (None, ""):

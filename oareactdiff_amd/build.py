@@ -9,7 +9,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.environ.get("OARD_LIB") or os.path.join(CSRC, "liboard_hip.so")
 # translation units -> the headers each one includes (None = every header of csrc/ except the ones another unit owns).  Units are compiled
 # to objects side by side and linked; an edit recompiles only the units that include the edited file.
-_EDGE = ["oard_engine.h", "oard_layout.h", "oard_kernels.h", "oard_edge_v1.h", "oard_inst.h"]
+_EDGE = ["oard_engine.h", "oard_layout.h", "oard_rbf_table.h", "oard_kernels.h", "oard_edge_v1.h", "oard_inst.h"]
 SOURCES = {
     "oard_hip.hip": None,                                                        # host code + every kernel not listed below
     "oard_general.hip": ["oard_general.h"],                                       # general-edge-list path

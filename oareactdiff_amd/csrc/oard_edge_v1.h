@@ -654,12 +654,19 @@ struct EquiStream {
 // of q (th = 1: the factor of vec[src], leftnet.py:263-270) only ever multiplies zeros, so its HT slots are neither computed nor stored
 // and the node stage does not read them.  The packed stream is unchanged: the executed slots are 3 tt + {0, 2}, the prefetch names the
 // NEXT EXECUTED slot's group, and the slab parity counts executed phases (`p`), not stream positions.
-template <class D, int WAVES, bool TRAIN>
+// RBT (inference only; FwdPlan::rbf_table): cr = rbf_proj(rbf) comes from the layer's table in u = exp(-d) (oard_rbf_table.h) instead of
+// an MFMA chain over rb - 24 of the 172 MFMAs and 6 of the 44 LDS-DMA pieces of a T2 phase, and the 24 registers of rb.  `rbuf` is then
+// the per-row records of k_rbf ([A][RBT_ROW]: interval, Hermite weights x rb x mask) and `rtab` the table.  The packed stream is
+// unchanged: a T2 phase fetches the first 1 + D1T chunks of its group.  The 16 table entries of a lane (two points x (f, h f') x 4
+// channels) are loaded behind the phase barrier for the NEXT executed slot, like the stores; cr is four FMAs per value at the phase start.
+template <class D, int WAVES, bool TRAIN, bool RBT = false>
 __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const float* __restrict__ stream,
                                                              const float* __restrict__ dp0b,
                                                              const float* __restrict__ ew, const float* __restrict__ rbuf,
                                                              float* __restrict__ qbuf, float* __restrict__ zd1,
-                                                             float* __restrict__ cdbuf, ActList al, int skip_mid) {
+                                                             float* __restrict__ cdbuf, ActList al, int skip_mid,
+                                                             const float* __restrict__ rtab) {
+    static_assert(!RBT || !TRAIN, "the training-mode forward keeps the MFMA chain (its backward differentiates rbf_proj)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using S = EquiStream<D>;
     constexpr int WB = D::WB, D1T = D::D1T, RB = D::RB, HT = D::HT, G1 = S::G1, G2 = S::G2;
@@ -675,7 +682,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const f
         pf.begin(stream, smem, ph, ph * G1, G1);
     };
     auto pf_begin_t2 = [&](int ph, int slot) {
-        pf.begin(stream, smem, ph, S::C1 + slot * G2, slot < S::NG2 ? G2 : 0);
+        pf.begin(stream, smem, ph, S::C1 + slot * G2, slot < S::NG2 ? (RBT ? 1 + D1T : G2) : 0);
     };
     auto next_slot = [&](int i) -> int { return i + ((skip && i % 3 == 0) ? 2 : 1); };    // slot executed after slot i (th = 1 left out)
     auto hook = [&]() { pf.tick(); };
@@ -693,9 +700,30 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const f
     f4 d1[D1T];
 #pragma unroll
     for (int t = 0; t < D1T; ++t) d1[t] = ld_vec(dp0b, t, lane);
-    f4 rb[RB];
+    f4 rb[RBT ? 1 : RB];
+    // RBT: this lane's entries of slot 0 (tn, prefetched), the Hermite weights x factor of its column (hw) and its place in a slot's table.
+    // Padding columns read interval 0 with zero weights (the spare record is never written).
+    f4 tn[RBT ? 4 : 1], hw = f4zero();
+    const float* tlane = nullptr;
+    auto ld_tab = [&](int slot) {
+        if constexpr (RBT) {
+            const float* t = tlane + (size_t)slot * ((size_t)(RBT_N + 1) * 32);
+            tn[0] = ld_f4(t); tn[1] = ld_f4(t + 4); tn[2] = ld_f4(t + 32); tn[3] = ld_f4(t + 36);
+        }
+    };
+    if constexpr (RBT) {
+        int idx = 0;
+        if (live) {
+            const f4 r0 = ld_f4(rbuf + a * RBT_ROW);
+            idx = min(max(__float_as_int(r0.x), 0), RBT_N - 1);
+            hw = (f4){r0.y, r0.z, r0.w, rbuf[a * RBT_ROW + 4]};
+        }
+        tlane = rtab + ((size_t)idx * 4 + g) * 8;
+        ld_tab(0);
+    } else {
 #pragma unroll
-    for (int b = 0; b < RB; ++b) rb[b] = ld_blk(rbuf, a, D::RP, b, lane);
+        for (int b = 0; b < RB; ++b) rb[b] = ld_blk(rbuf, a, D::RP, b, lane);
+    }
     f4 xn = ld_f4(erow);
     pf_begin(0);
     pf.flush();
@@ -731,7 +759,16 @@ __global__ __launch_bounds__(WAVES * 64) void k_equi_edge_v1(TopoDev tp, const f
         pf_begin_t2(p + 1, next_slot(i));
         const int tt = i / 3, th = i - 3 * tt;
         f4 cd, cr;
-        if (decltype(rows4)::value) {                          // the 13th tile of every third: 4 real rows, 4x4x1 MFMAs
+        if constexpr (RBT) {                                   // this slot's entries landed with the barrier; then fetch the next slot's
+            cr = hw.x * tn[0] + hw.y * tn[1] + hw.z * tn[2] + hw.w * tn[3];
+            if (next_slot(i) < S::NG2) ld_tab(next_slot(i));
+            if (decltype(rows4)::value) {
+                cd = reduce_g(chain_tile4<D1T>(SL(p), 1, d1, A(p, 0), hook));
+                if (g != 0) cd = f4zero();                     // (the table is zero on the padding channels)
+            } else {
+                cd = chain_tile<D1T>(SL(p), 1, d1, A(p, 0), hook);
+            }
+        } else if (decltype(rows4)::value) {                   // the 13th tile of every third: 4 real rows, 4x4x1 MFMAs
             cd = reduce_g(chain_tile4<D1T>(SL(p), 1, d1, A(p, 0), hook));
             cr = reduce_g(chain_tile4<RB>(SL(p), 1 + D1T, rb, f4zero(), hook));
             if (g != 0) { cd = f4zero(); cr = f4zero(); }

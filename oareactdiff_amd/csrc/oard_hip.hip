@@ -76,6 +76,7 @@ int g_npb = 0;              // nodes per workgroup of the node stages (0 = auto,
 int g_poison = 0;           // 1: fill the workspace with NaN bit patterns before every forward (tests: nothing may depend on its contents)
 int g_gcl_msum_taken = 0;   // did the last forward sum the messages inside the edge kernels (tests: oard_debug_option("gcl_msum_taken", 0) == OARD_OK)
 int g_equi_l0_taken = 0;    // did the last forward take that shortcut (tests: oard_debug_option("equi_l0_taken", 0) == OARD_OK)
+int g_equi_rbf_taken = 0;   // did EVERY layer of the last forward take rbf_proj from its table (tests: oard_debug_option("equi_rbf_taken", 0) == OARD_OK)
 int g_parts = 0;            // sub-batches per topology (0 = auto: 4 for B >= 32, 2 for B >= 16, else 1)
 int g_wgrad_shapes = 3;       // bit k: workgroup shape kWglShapes[k] of the LDS-panel kernel may be chosen (A/B: debug option wgrad_shapes)
 int g_wgrad_t16 = 256;       // workgroups per weight-gradient GEMM of the 16 x 16-tile kernel (oard_wgrad_t16.h; 0: never use it)
@@ -182,6 +183,7 @@ PackOff make_layout(const oard_config* c) {
         lo.dp0 = mat(d.D1T, d.WB); lo.dp0b = take(d.D1P);
         lo.dp2 = mat(3 * d.HT, d.D1T); lo.dp2b = take(3 * d.HP);
         lo.rbfp = mat(3 * d.HT, d.RB);
+        lo.rbfw = take((size_t)3 * d.H * d.R); lo.rbff = take(4);
         lo.vp = mat(2 * d.HT, d.HT);
         lo.xv0 = mat(d.HT, 2 * d.HT);
         lo.xv2 = mat(3 * d.HT, d.HT);
@@ -196,6 +198,8 @@ PackOff make_layout(const oard_config* c) {
             lo.equi_b3 = take((size_t)(nbw * 3 * d.D1T + ((d.RB + 1) / 2 + (d.D1T + 1) / 2) * 9 * d.HT) * 256);
         }
     }
+    po.head = cur;
+    for (int l = 0; l < c->num_layers; ++l) po.layer[l].rbft = take(rbt_layer_floats(d.HT));
     po.total = cur;
     po.signed_scal = c->reflect_equiv ? 0 : 1;
     for (int l = 0; l < c->num_layers; ++l) po.layer[l].xcross = c->reflect_equiv ? 0 : 1;
@@ -299,6 +303,46 @@ struct Packer {
         return OARD_OK;
     }
 };
+// ---- rbf_proj tables of a blob (oard_rbf_table.h, k_rbf_table_fill / _check) ---------------------------------------------------------------
+// oard_pack_weights does not build them - a trainer packs every update and never reads them.  The first inference forward on a blob
+// that could take them fills and checks them on its stream and reads the per-layer flags ONCE (a stream synchronisation, like the
+// first call's other one-time work); later calls find the answer here.  Every pack of a blob forgets its entry.  A call that is being
+// captured into a graph cannot synchronise: it runs without the tables unless an earlier eager call built them.
+struct RbfTablesOf { const void* blob; unsigned good; };
+static std::mutex g_rbf_mu;
+static std::vector<RbfTablesOf> g_rbf_known;
+static void rbf_tables_forget(const void* blob) {
+    std::lock_guard<std::mutex> lk(g_rbf_mu);
+    g_rbf_known.erase(std::remove_if(g_rbf_known.begin(), g_rbf_known.end(), [&](const RbfTablesOf& e) { return e.blob == blob; }), g_rbf_known.end());
+}
+static int rbf_tables_for(const oard_config* c, const PackOff& po, const float* blob, hipStream_t st, unsigned* good) {
+    *good = 0;
+    std::lock_guard<std::mutex> lk(g_rbf_mu);
+    for (const RbfTablesOf& e : g_rbf_known) if (e.blob == blob) { *good = e.good; return OARD_OK; }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return OARD_OK;
+    const RDims d(c->hidden, c->num_radial);
+    RbtJobs j;
+    memset(&j, 0, sizeof(j));
+    for (int l = 0; l < c->num_layers; ++l) { j.w[l] = po.layer[l].rbfw; j.tab[l] = po.layer[l].rbft; j.flag[l] = po.layer[l].rbff; }
+    j.means = po.rbf_means; j.betas = po.rbf_betas; j.H = d.H; j.HT = d.HT; j.R = d.R;
+    hipLaunchKernelGGL(k_rbf_table_fill, dim3((unsigned)cdiv((long long)3 * d.HT * (RBT_N + 1) * 4, 256), (unsigned)c->num_layers), dim3(256), 0, st,
+                       const_cast<float*>(blob), j);
+    hipLaunchKernelGGL(k_rbf_table_check, dim3((unsigned)(3 * d.HT * 4), (unsigned)c->num_layers), dim3(256), 0, st, const_cast<float*>(blob), j);
+    HIP_TRY(hipGetLastError());
+    std::vector<float> flags((size_t)c->num_layers, 0.f);
+    for (int l = 0; l < c->num_layers; ++l)
+        HIP_TRY(hipMemcpyAsync(&flags[l], blob + po.layer[l].rbff, sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    unsigned mask = 0;
+    for (int l = 0; l < c->num_layers; ++l) if (flags[l] == 1.0f) mask |= 1u << l;
+    if (g_rbf_known.size() >= 64) g_rbf_known.erase(g_rbf_known.begin());
+    g_rbf_known.push_back({blob, mask});
+    *good = mask;
+    return OARD_OK;
+}
+
 // scratch of the stage-split latency path (activations between the stage launches)
 #define OARD_SMALL_MAX_EDGES (512 * 16 * 16)      // topologies up to 131 072 edges get the scratch buffer
 static WsOff make_ws(const oard_config* c, const TopoDev& td) {
@@ -324,6 +368,7 @@ static WsOff make_ws(const oard_config* c, const TopoDev& td) {
     // scratch of the stage-split latency edge kernels: only topologies small enough to ever take that path (the launch-shape
     // thresholds are run-time options, so the plan is told whether the buffer exists)
     w.small_a = E <= (size_t)OARD_SMALL_MAX_EDGES ? take(A * d.D1P * 4) : 0;
+    w.rbt = take(A * RBT_ROW * 4);
     w.total = cur;
     return w;
 }
@@ -415,7 +460,8 @@ int launch_gcl_v1(const GclLayer& g, bool msum, const GclArgs& a) {
 // inner row.  Under FwdPlan::l0_skip the 8-wave streamed kernel leaves out the middle third of q in layer 0.)
 template <class D>
 int launch_equi_v1(const FwdPlan& plan, int l, const TopoDev& tp, const float* wb, const LayerOff& lo, const float* stream, const float* dp0b,
-                   const float* ew, const float* rbuf, float* qbuf, float* zd1, float* cd, hipStream_t st, float* d1s, float* small, ActList al) {
+                   const float* ew, const float* rbuf, float* qbuf, float* zd1, float* cd, hipStream_t st, float* d1s, float* small, ActList al,
+                   const float* rbt) {
     const long long tiles = cdiv(tp.A, 16);
     switch (plan.equi) {
         case EQ_TRAIN_B3:
@@ -424,7 +470,7 @@ int launch_equi_v1(const FwdPlan& plan, int l, const TopoDev& tp, const float* w
             return OARD_OK;
         case EQ_TRAIN:
             LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 8, true>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiStream<D>::LDS_BYTES), st,
-                       tp, stream, dp0b, ew, rbuf, qbuf, zd1, cd, ActList{}, 0);
+                       tp, stream, dp0b, ew, rbuf, qbuf, zd1, cd, ActList{}, 0, (const float*)nullptr);
             return OARD_OK;
         case EQ_SMALL_SPLIT:     // stage-split latency path: 2 launches, few tiles only
             LAUNCH_LDS(F_EQUI_EDGE, (k_equi_small_s1<D, 8>), tiles * cdiv(D::D1T, 8), 512, (size_t)D::WB * 1024, st, tp, wb, lo, ew, small);
@@ -440,11 +486,15 @@ int launch_equi_v1(const FwdPlan& plan, int l, const TopoDev& tp, const float* w
             return OARD_OK;
         case EQ_W4:
             LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 4, false>), cdiv(tp.A, 16 * 4), 4 * 64, (EquiStream<D>::LDS_BYTES), st,
-                       tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al, 0);
+                       tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al, 0, (const float*)nullptr);
             return OARD_OK;
         case EQ_W8:
-            LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 8, false>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiStream<D>::LDS_BYTES), st,
-                       tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al, plan.l0_skip && l == 0 ? 1 : 0);
+            if (plan.rbf_table[l])   // rbf_proj from the layer's table: `rbt` = the per-row records of k_rbf in place of the radial basis
+                LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 8, false, true>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiStream<D>::LDS_BYTES), st,
+                           tp, stream, dp0b, ew, rbt, qbuf, nullptr, nullptr, al, plan.l0_skip && l == 0 ? 1 : 0, wb + lo.rbft);
+            else
+                LAUNCH_LDS(F_EQUI_EDGE, (k_equi_edge_v1<D, 8, false>), cdiv(tp.A, 16 * 8), 8 * 64, (EquiStream<D>::LDS_BYTES), st,
+                           tp, stream, dp0b, ew, rbuf, qbuf, nullptr, nullptr, al, plan.l0_skip && l == 0 ? 1 : 0, (const float*)nullptr);
             return OARD_OK;
         default: return OARD_EINVAL;
     }
@@ -525,7 +575,13 @@ static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoP
     const long long N = tp.N, E = tp.E, A = tp.A;
     const unsigned gN = (unsigned)cdiv(N, 64), gA = (unsigned)cdiv(A, 64);
     const double cutoff = (double)c->cutoff;
-    const FwdPlan plan = make_fwd_plan({opt, c->precision, train, topo->conc, tp.npb, device_cus(), A, E, tp.CI, tp.CX, c->num_layers, w.small_a != 0});
+    FwdPlanIn plan_in{opt, c->precision, train, topo->conc, tp.npb, device_cus(), A, E, tp.CI, tp.CX, c->num_layers, w.small_a != 0};
+    // rbf_proj tables: only a call that could take them (plan_rbf_wanted) asks for them - the first such call on a blob builds them
+    if (plan_rbf_wanted(plan_in)) { const int rc = rbf_tables_for(c, po, wb, st, &plan_in.rbf_good); if (rc != OARD_OK) return rc; }
+    const FwdPlan plan = make_fwd_plan(plan_in);
+    bool any_rbt = false, all_rbt = c->num_layers > 0;
+    for (int l = 0; l < c->num_layers; ++l) { any_rbt = any_rbt || plan.rbf_table[l]; all_rbt = all_rbt && plan.rbf_table[l]; }
+    g_equi_rbf_taken = all_rbt;
     const bool msum = plan.msum, use_al = plan.use_al, nv1 = plan.node != NODE_V0;
     const int stop_after = train ? 0 : g_stop_after;
     // the inner rows inside the cutoff, compacted per call (plan.use_al): inference with the streamed edge kernels and the v1 node stages;
@@ -548,7 +604,7 @@ static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoP
         LAUNCH(F_INIT, k_edge_geo, cdiv(A, 256), 256, st, tp, (const float*)pos, (const double*)pf64, cutoff, geo, d64, use_al ? al_cnt : nullptr);
         if (use_al) LAUNCH(F_INIT, k_active_list, cdiv(A, 256), 256, st, tp, (const float*)geo, (const int*)al_cnt, (int*)al.rows, (int*)al.src, (int*)al.pre, (int*)al.n);
         LAUNCH(F_INIT, k_rbf, cdiv(A * D::RP, 256), 256, st, tp, (const double*)d64, (const float*)geo,
-               wb + po.rbf_means, wb + po.rbf_betas, cutoff, rbuf, ew, D::R, D::RP, D::H, D::WP);
+               wb + po.rbf_means, wb + po.rbf_betas, cutoff, rbuf, ew, D::R, D::RP, D::H, D::WP, any_rbt ? (float*)(ws + w.rbt) : (float*)nullptr);
     }
     LAUNCH(F_INIT, (k_node_embed<D>), gN, 256, st, tp, wb, po, (const float*)hin, zemb, nb);
     if (A > 0) LAUNCH(F_INIT, (k_radial_lin<D>), gA, 256, st, tp, wb, po, (const float*)rbuf, (const float*)geo, ew);
@@ -608,7 +664,7 @@ static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoP
             if (A > 0) {
                 rc = launch_equi_v1<D>(plan, l, tp, wb, lo, wb + lo.equi_stream, wb + lo.dp0b, ew_out, rbuf, vmsg,
                                        train ? (float*)(tape + to.zd1[l]) : nullptr, train ? (float*)(tape + to.cd[l]) : nullptr, st,
-                                       (float*)(ws + w.d1s), (float*)(ws + w.small_a), al);
+                                       (float*)(ws + w.d1s), (float*)(ws + w.small_a), al, (const float*)(ws + w.rbt));
                 if (rc != OARD_OK) return rc;
             }
 #define EQUI_NODE_V1(D_, ROWS_, XC_) LAUNCH(F_NODE, (k_equi_node_v1<D_, NW, ROWS_, XC_>), gN16, NW * 64, st, tp, wb, lo, (const float*)vmsg, \
@@ -830,7 +886,8 @@ int oard_pack_weights(const oard_config* c, const float* const* params, size_t n
     const RDims d(c->hidden, c->num_radial);
     const int H = d.H, R = d.R, W = d.W, C = c->in_hidden, emb = embed_dim(c);
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(packed, 0, po.total * sizeof(float), st));
+    rbf_tables_forget(packed);                  // (built again by the first inference forward that wants them: rbf_tables_for)
+    HIP_TRY(hipMemsetAsync(packed, 0, po.head * sizeof(float), st));
     Packer pk{params, (float*)packed, st, {}, 0};
 
     pk.nat(pi.emb_w, C, 0, H, C, d.HT, 1, po.emb);          pk.vec(pi.emb_b, H, d.HP, 1, d.HP, po.emb_b);
@@ -885,6 +942,7 @@ int oard_pack_weights(const oard_config* c, const float* const* params, size_t n
         pk.nat(m + 4, H, 0, H, H, d.HT, d.HT, lo.xp0);
         pk.matrix(m + 5, H, 0, H, d.HP, 3, H, d.HP, 1, 3 * d.HT, d.HT, lo.xp2);
         pk.matrix(m + 6, R, 0, H, d.HP, 3, R, d.RP, 1, 3 * d.HT, d.RB, lo.rbfp);
+        pk.raw(m + 6, 3 * H * R, lo.rbfw);
         pk.vec(m + 7, H, d.HP, 1, d.HP, lo.ln_q_w);          pk.vec(m + 8, H, d.HP, 1, d.HP, lo.ln_q_b);
         const int u = pi.upd0 + 9 * l;    // vec_proj w | xvec_proj.0 w | xvec_proj.2 w | lin3.0 w,b | lin3.2 w,b | lin3.4 w,b
         pk.matrix(u + 0, H, 0, H, d.HP, 2, H, d.HP, 1, 2 * d.HT, d.HT, lo.vp);
@@ -2344,12 +2402,13 @@ int oard_debug_option(const char* name, int value) {
         {"gcl_variant", &g_fwd.gcl_variant}, {"equi_variant", &g_fwd.equi_variant}, {"node_variant", &g_fwd.node_variant},
         {"auto_small", &g_fwd.auto_small}, {"auto_tiny", &g_fwd.auto_tiny}, {"small_split", &g_fwd.small_split},
         {"gcl_persist", &g_fwd.gcl_persist}, {"gcl_grid", &g_fwd.gcl_grid}, {"gcl_skip", &g_fwd.gcl_skip}, {"equi_skip", &g_fwd.equi_skip},
-        {"equi_l0_skip", &g_fwd.equi_l0_skip}, {"gcl_msum", &g_fwd.gcl_msum},
+        {"equi_l0_skip", &g_fwd.equi_l0_skip}, {"gcl_msum", &g_fwd.gcl_msum}, {"equi_rbf_table", &g_fwd.equi_rbf_table},
         {"skip_families", &g_skip_families}, {"parts", &g_parts}, {"sequential", &g_sequential}, {"poison", &g_poison}, {"npb", &g_npb},
         {"wgrad_wgs", &g_wgrad_wgs}, {"wgrad_t16", &g_wgrad_t16}, {"wgrad_queue", &g_wgrad_queue}, {"gate_fold", &g_gate_fold},
         {"wgrad_lds", &g_wgrad_lds}, {"wgrad_shapes", &g_wgrad_shapes}, {"train_dual", &g_train_dual}};
     if (strcmp(name, "experiments") == 0) return kV0 ? OARD_OK : OARD_EINVAL;      // query: is this an experiment build?
     if (strcmp(name, "gcl_msum_taken") == 0) return g_gcl_msum_taken ? OARD_OK : OARD_EINVAL;      // query: did the last forward take that form?
+    if (strcmp(name, "equi_rbf_taken") == 0) return g_equi_rbf_taken ? OARD_OK : OARD_EINVAL;      // query: did every layer of the last forward take the table?
     if (strcmp(name, "equi_l0_taken") == 0) return g_equi_l0_taken ? OARD_OK : OARD_EINVAL;      // query: did the last forward skip it?
     for (const auto& e : table) {
         if (strcmp(name, e.name) != 0) continue;

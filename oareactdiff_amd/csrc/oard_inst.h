@@ -54,11 +54,11 @@ OARD_DIMS_LIST
 
 // ---- EquiMessage edge kernel + fused node stage, the two backward edge kernels (oard_edge_v1.h, oard_node_v1.h, oard_edge_bwd.h) ----------
 #if !defined(OARD_INST_DEFINE) || defined(OARD_INST_UNIT_EQUI)
-#define OARD_A_EQUI (TopoDev, const float*, const float*, const float*, const float*, float*, float*, float*, ActList, int)
+#define OARD_A_EQUI (TopoDev, const float*, const float*, const float*, const float*, float*, float*, float*, ActList, int, const float*)
 #define OARD_A_EQUI_NODE (TopoDev, const float*, LayerOff, const float*, const float*, const float*, const float*, const float*, float*, const float*, float*, float*, float*, ActList)
 #define X(h, r) \
     OARD_INST((k_equi_edge_v1<Dims<h, r>, 8, false>), OARD_A_EQUI) OARD_INST((k_equi_edge_v1<Dims<h, r>, 8, true>), OARD_A_EQUI) \
-    OARD_INST((k_equi_edge_v1<Dims<h, r>, 4, false>), OARD_A_EQUI) \
+    OARD_INST((k_equi_edge_v1<Dims<h, r>, 4, false>), OARD_A_EQUI) OARD_INST((k_equi_edge_v1<Dims<h, r>, 8, false, true>), OARD_A_EQUI) \
     OARD_INST((k_equi_node_v1<Dims<h, r>, OARD_NW(h), false, false>), OARD_A_EQUI_NODE) OARD_INST((k_equi_node_v1<Dims<h, r>, OARD_NW(h), false, true>), OARD_A_EQUI_NODE) \
     OARD_INST((k_equi_node_v1<Dims<h, r>, OARD_NW(h), true, false>), OARD_A_EQUI_NODE) OARD_INST((k_equi_node_v1<Dims<h, r>, OARD_NW(h), true, true>), OARD_A_EQUI_NODE) \
     OARD_INST((k_equi_node_v1<Layer0<Dims<h, r> >, OARD_NW(h), false, false>), OARD_A_EQUI_NODE) OARD_INST((k_equi_node_v1<Layer0<Dims<h, r> >, OARD_NW(h), false, true>), OARD_A_EQUI_NODE) \

@@ -3,6 +3,7 @@
 #pragma once
 #include "oard_engine.h"
 #include "oard_layout.h"
+#include "oard_rbf_table.h"
 
 #define GEO_STRIDE 12   // per inner edge: d, env, u[3], c[3], v[3], mask
 #define EPSF 1e-6
@@ -637,6 +638,69 @@ OARD_KERNEL __global__ __launch_bounds__(256) void k_lin3u_table_check(float* __
         }
     }
 }
+// ---- rbf_proj of EquiMessage as a table in u = exp(-d) (oard_rbf_table.h) ---------------------------------------------------------------
+// Built from the raw rbf_proj weights [3 H][R] and the means / betas kept in the blob, for the layers of ONE blob, when an inference
+// forward first wants it (oard_hip.hip: rbf_tables_for) - never by oard_pack_weights itself, which a trainer calls every update.
+// flag block of a layer (4 floats): [table is good, channel groups that failed, blocks done, -]
+struct RbtJobs { size_t w[OARD_MAX_LAYERS], tab[OARD_MAX_LAYERS], flag[OARD_MAX_LAYERS]; size_t means, betas; int H, HT, R; };
+// one thread per (slot, point, g): the 4 channels of a lane's fragment, value and step x derivative from the float64 sum
+OARD_KERNEL __global__ __launch_bounds__(256) void k_rbf_table_fill(float* __restrict__ blob, RbtJobs j) {
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= (long long)3 * j.HT * (RBT_N + 1) * 4) return;
+    const int l = blockIdx.y, g = (int)(id & 3), pt = (int)((id >> 2) % (RBT_N + 1)), slot = (int)((id >> 2) / (RBT_N + 1));
+    const int tt = slot / 3, th = slot - 3 * tt;
+    float* out = blob + j.tab[l] + ((size_t)slot * (RBT_N + 1) + pt) * 32 + 8 * g;
+    const double u = (double)pt * (1.0 / RBT_N);
+    for (int s = 0; s < 4; ++s) {
+        const int feat = 16 * tt + 4 * g + s;
+        float f32 = 0.f, d32 = 0.f;
+        if (feat < j.H) {
+            double f, df;
+            rbt_eval_f64(blob + j.w[l] + (size_t)(th * j.H + feat) * j.R, blob + j.means, blob + j.betas, j.R, u, f, df);
+            rbt_entry(f, df, f32, d32);
+        }
+        out[s] = f32; out[4 + s] = d32;
+    }
+    if (id == 0) { float* fl = blob + j.flag[l]; fl[0] = 0.f; fl[1] = 0.f; fl[2] = 0.f; fl[3] = 0.f; }
+}
+// one workgroup per (slot, g): every interval's midpoint, evaluated in float64 from the stored float32 entries, against the float64 sum;
+// a channel passes with a worst deviation of at most RBT_TOL of its range.  The last workgroup of a layer to finish sets the flag.
+OARD_KERNEL __global__ __launch_bounds__(256) void k_rbf_table_check(float* __restrict__ blob, RbtJobs j) {
+    __shared__ double red_e[4][256], red_f[4][256];
+    const int l = blockIdx.y, slot = blockIdx.x >> 2, g = blockIdx.x & 3, t = threadIdx.x;
+    const int tt = slot / 3, th = slot - 3 * tt;
+    const float* tab = blob + j.tab[l] + (size_t)slot * (RBT_N + 1) * 32 + 8 * g;
+    for (int s = 0; s < 4; ++s) {
+        const int feat = 16 * tt + 4 * g + s;
+        double e = 0.0, fm = 0.0;
+        if (feat < j.H)
+            for (int i = t; i < RBT_N; i += 256) {
+                const float* p0 = tab + (size_t)i * 32 + s;
+                double f, df;
+                rbt_eval_f64(blob + j.w[l] + (size_t)(th * j.H + feat) * j.R, blob + j.means, blob + j.betas, j.R, ((double)i + 0.5) * (1.0 / RBT_N), f, df);
+                const double dev = fabs(rbt_midpoint(p0[0], p0[4], p0[32], p0[36]) - f);
+                e = dev > e || dev != dev ? dev : e;                 // (a NaN stays and fails the test below)
+                fm = fmax(fm, fmax(fabs((double)p0[0]), fabs(f)));
+            }
+        red_e[s][t] = e; red_f[s][t] = fm;
+    }
+    __syncthreads();
+    if (t == 0) {
+        bool ok = true;
+        for (int s = 0; s < 4; ++s) {
+            double e = 0.0, fm = 0.0;
+            for (int k = 0; k < 256; ++k) { e = red_e[s][k] > e || red_e[s][k] != red_e[s][k] ? red_e[s][k] : e; fm = fmax(fm, red_f[s][k]); }
+            ok = ok && (16 * tt + 4 * g + s >= j.H || rbt_channel_ok(e, fm));
+        }
+        unsigned* u = reinterpret_cast<unsigned*>(blob + j.flag[l]);
+        if (!ok) atomicAdd(u + 1, 1u);
+        __threadfence();
+        if (atomicAdd(u + 2, 1u) == gridDim.x - 1) {
+            __threadfence();
+            blob[j.flag[l]] = atomicAdd(u + 1, 0u) == 0u ? 1.0f : 0.0f;
+        }
+    }
+}
 // Zeroes up to 64 short rows in one launch (the spare rows of the training tape, oard_hip.hip: forward_impl)
 struct ZeroRows { float* p[64]; int n[64]; int count; };
 OARD_KERNEL __global__ __launch_bounds__(256) void k_zero_rows(ZeroRows z) {
@@ -674,7 +738,7 @@ OARD_KERNEL __global__ __launch_bounds__(256) void k_active_list(TopoDev tp, con
 }
 OARD_KERNEL __global__ void k_rbf(TopoDev tp, const double* __restrict__ d64, const float* __restrict__ geo,
                       const float* __restrict__ means, const float* __restrict__ betas, double cutoff,
-                      float* __restrict__ rbuf, float* __restrict__ ew, int R, int RP, int H, int WP) {
+                      float* __restrict__ rbuf, float* __restrict__ ew, int R, int RP, int H, int WP, float* __restrict__ rbt = nullptr) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= tp.A * RP) return;
     const long long a = i / RP;
@@ -682,6 +746,14 @@ OARD_KERNEL __global__ void k_rbf(TopoDev tp, const double* __restrict__ d64, co
     float v = 0.f;
     if (k < R) {
         const double d = d64[a], m = (double)geo[a * GEO_STRIDE + 11];
+        if (rbt != nullptr && k == 1) {              // the row's place in the rbf_proj table (oard_rbf_table.h): interval and Hermite weights x rb x mask
+            const RbtAt at = rbt_locate(d, cutoff, m);
+            float w[4];
+            rbt_weights(at, w);
+            float* r = rbt + a * RBT_ROW;
+            st_f4(r, (f4){__int_as_float(at.idx), w[0], w[1], w[2]});
+            st_f4(r + 4, (f4){w[3], 0.f, 0.f, 0.f});
+        }
         double rb = 0.5 * (cos(d * M_PI / cutoff) + 1.0);
         rb = d < cutoff ? rb : 0.0;
         const double q = exp(-d) - (double)means[k];

@@ -48,6 +48,9 @@ struct LayerOff {
     size_t ln_g_w, ln_g_b, W1a, b1, W1b, W1c, W2, b2, watt, batt, W3, b3, nm0, nm0b, nm1, nm1b;
     // EquiMessage (leftnet.py:186-289)
     size_t ln_q_w, ln_q_b, xp0, xp2, dp0, dp0b, dp2, dp2b, rbfp;
+    // rbf_proj as a table in exp(-d) (oard_rbf_table.h): the raw weights [3 H][R] it is built from, its flag block (4 floats, zeroed by
+    // every pack) and the table itself - behind PackOff::head, where oard_pack_weights never writes: built for inference forwards only
+    size_t rbfw, rbff, rbft;
     // EquiUpdate (leftnet.py:292-346)
     size_t vp, xv0, xv2, l3u;   // l3u raw: w0[48*3] b0[48] w2[8*48] b2[8] w4[8] b4[1]
     size_t l3t;                 // the frame-scalar MLP as a table (k_lin3u_table): [L3T_N + 1] x (f, f' h), then the "table is good" flag
@@ -66,6 +69,7 @@ struct PackOff {
     size_t rbf_means, rbf_betas;  // [RP]
     size_t enc[OARD_MAX_OBJECTS], dec[OARD_MAX_OBJECTS];  // raw MLP blocks
     LayerOff layer[OARD_MAX_LAYERS];
+    size_t head;      // floats oard_pack_weights clears and fills; [head, total) are the rbf_proj tables
     size_t total;
     int signed_scal;  // reflect_equiv = False: no |.| on the second frame component of the edge scalarisation (leftnet.py:794-796)
 };
@@ -154,6 +158,7 @@ struct WsOff {
     size_t pos, pf64, pf32, x1, pp0, labels, hin, zemb, nb, s, s1, ne1, xh, P, Q, xq, vec, vec2, v2buf, sc0, vdot,
         geo, d64, rbuf, ew, mbuf, xmsg, vmsg, dpos, hout, total;   // xmsg..vmsg double as qbuf [A][3][HP] (v1)
     size_t al_rows, al_src, al_pre, al_cnt, al_n;   // ActList of this call + the per-block counts it is built from
+    size_t rbt;                    // [A + 1][RBT_ROW] per inner row: interval and Hermite weights x envelope x mask of the rbf_proj table (k_rbf)
     size_t d1s;                    // split-precision EquiMessage kernel: SiLU(d1) in wave-tile order, [ceil(A / 128) * 8][D1T][256] floats
     size_t small_a;                // stage-split EquiMessage latency path: d1 [A+1][D1P]; 0 = not allocated (large topologies)
 };

@@ -23,6 +23,7 @@ struct FwdOptions {
     int equi_skip = 1;       // EquiMessage runs the inner edges inside the cutoff only (ActList; exact: it is zero on the others)
     int equi_l0_skip = 1;    // 0: layer 0 runs the whole EquiMessage like every other layer (A/B and tests; FwdPlan::l0_skip)
     int gcl_msum = 1;        // 0: the GCL edge kernels store one message row per edge and the node stage gathers them (A/B and tests; FwdPlan::msum)
+    int equi_rbf_table = 1;  // 0: EquiMessage's rbf_proj always runs as an MFMA chain, never from its table in exp(-d) (A/B and tests; FwdPlan::rbf_table)
 };
 
 enum GclShape {
@@ -46,6 +47,7 @@ struct FwdPlanIn {
     long long A, E, CI, CX;  // inner edges, edges, columns of the inner / inter-object list (TopoDev)
     int num_layers;
     bool scratch;            // the stage-split scratch exists (WsOff::small_a)
+    unsigned rbf_good = 0;   // bit l: layer l's rbf_proj table exists in the blob and passed its check (oard_rbf_table.h); 0 = none built
 };
 struct FwdPlan {
     int num_layers;
@@ -64,6 +66,9 @@ struct FwdPlan {
     // layer 0 of an inference forward: vec is exactly zero there, so the third of q that only multiplies vec[src] is neither computed
     // (8-wave streamed fp32 edge kernel) nor gathered (large-batch node stage) - both or neither.  The training-mode forward tapes it.
     bool l0_skip;
+    // per layer: the 8-wave streamed fp32 EquiMessage kernel of an inference forward takes rbf_proj from the layer's table in exp(-d)
+    // instead of an MFMA chain - only where that table passed its check (FwdPlanIn::rbf_good).  The training-mode forward never does.
+    bool rbf_table[16];   // [OARD_MAX_LAYERS]
     const GclLayer& gcl_at(int l) const { return gcl[(l == 0 ? 1 : 0) | (l == num_layers - 1 ? 2 : 0)]; }
 };
 
@@ -114,6 +119,10 @@ inline EquiShape plan_equi_shape(const FwdPlanIn& in) {
         default: return EQ_INVALID;
     }
 }
+// could this call take rbf_proj from its tables if they are good?  (forward_impl asks for FwdPlanIn::rbf_good only then)
+inline bool plan_rbf_wanted(const FwdPlanIn& in) {
+    return !in.train && in.opt.equi_rbf_table && in.A > 0 && plan_equi_shape(in) == EQ_W8;
+}
 // The training-mode forward has one shape per stage: variants 2 / 2 / 1, the layer-0 / last-layer shortcuts of the GCL always on.
 inline FwdPlan make_fwd_plan(FwdPlanIn in) {
     if (in.train) { in.opt.gcl_variant = in.opt.equi_variant = 2; in.opt.node_variant = 1; in.opt.gcl_skip = 1; }
@@ -128,6 +137,8 @@ inline FwdPlan make_fwd_plan(FwdPlanIn in) {
     p.equi = plan_equi_shape(in);
     p.use_al = !in.train && o.equi_skip && in.A > 0 && nv1;
     p.l0_skip = !in.train && o.equi_l0_skip && in.A > 0 && p.node == NODE_LARGE && p.equi == EQ_W8;
+    for (int l = 0; l < 16; ++l)
+        p.rbf_table[l] = !in.train && o.equi_rbf_table && in.A > 0 && p.equi == EQ_W8 && l < in.num_layers && ((in.rbf_good >> l) & 1u);
     auto throughput = [&](long long n) { const GclShape s = plan_gcl_shape(in, n); return n == 0 || s == GCL_PERSIST || s == GCL_RING3; };
     p.msum = !in.train && o.gcl_msum && in.E > 0 && o.gcl_variant == 2 && p.node == NODE_LARGE && throughput(in.CI) && throughput(in.CX);
     // Inner edges run every stage; inter-object edges skip S1 in the first layer (constant initial state) and S3 in the last (their
