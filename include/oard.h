@@ -462,6 +462,25 @@ int oard_adamw_step_dev(float* param_dev, const float* grad_dev, float* exp_avg_
                         double* clip_state_dev, int capacity, const float* grad_norm_dev, const float* flag_dev, float* out4_dev,
                         oard_stream_t stream);
 
+/* The exponential moving average of the weights, updated after every batch (trainer/ema.py:37-47: EMACallback.on_train_batch_end ->
+ * timm's ModelEmaV2.update, wired in trainer/train_ts1x.py:188-189), in float32:
+ *     ema[i] = fl(fl(d32 ema[i]) + fl(w32 param[i])),  d32 = (float)ema_decay, w32 = (float)(1.0 - ema_decay)
+ * - two rounded products and one add, no fused multiply-add: the bits torch gives for `decay * e + (1. - decay) * m`.  `ema_decay` is
+ * timm's decay, the weight of the OLD average (the reference's EMACallback(decay=x) passes 1 - x, ema.py:29).  ema_dev: n floats that do
+ * not overlap param_dev.  A null ema_dev or a decay outside [0, 1] returns OARD_EINVAL and launches nothing.
+ * oard_adamw_step_ema / oard_adamw_step_dev_ema: oard_adamw_step / oard_adamw_step_dev (same arguments, same parameters and moments bit
+ * for bit) with the line above applied to the freshly stepped parameter in the same kernel - no extra launch; a skipped step
+ * (oard_adamw_step_dev_ema) leaves the average untouched like everything else.
+ * oard_ema_update: the line alone, for callers that step the weights by other means.  Asynchronous on `stream`. */
+int oard_adamw_step_ema(float* param_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* max_exp_avg_sq_dev,
+                        int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, int amsgrad,
+                        double grad_scale, float* ema_dev, double ema_decay, oard_stream_t stream);
+int oard_adamw_step_dev_ema(float* param_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* max_exp_avg_sq_dev,
+                            int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, int amsgrad, int clip,
+                            double* clip_state_dev, int capacity, const float* grad_norm_dev, const float* flag_dev, float* out4_dev,
+                            float* ema_dev, double ema_decay, oard_stream_t stream);
+int oard_ema_update(float* ema_dev, const float* param_dev, int64_t n, double ema_decay, oard_stream_t stream);
+
 /* The library's own streams of the current device (three non-blocking streams, chosen once per device so that each runs on a hardware
  * queue of its own beside the caller's stream - the runtime serves a process's streams from 4 queues): 0 = the training sweep's
  * gradient stream (and the second sub-batch of a multi-part forward), 1 = the third sub-batch, 2 = topology uploads (and the fourth).

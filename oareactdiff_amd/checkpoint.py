@@ -215,12 +215,31 @@ def _plain(x: Any) -> Any:
     return x
 
 
+def ema_state_from_checkpoint(ckpt: Mapping) -> Mapping[str, torch.Tensor]:
+    """The averaged weights a run with the reference's `EMACallback` leaves in its checkpoint: Lightning stores every callback's
+    `state_dict()` under `callbacks[<callback key>]`, and that callback's is `{"state_dict_ema": ...}` (trainer/ema.py:73-75), keyed
+    like the LightningModule's own state dict.  The first callback entry that has the key is taken."""
+    callbacks = _plain(ckpt.get("callbacks") or {})
+    for state in (callbacks.values() if isinstance(callbacks, Mapping) else ()):
+        state = _plain(state)
+        if isinstance(state, Mapping) and "state_dict_ema" in state:
+            return _plain(state["state_dict_ema"])
+    raise KeyError("checkpoint holds no EMA weights: no entry of `callbacks` has a `state_dict_ema` (it was not written with the "
+                   "reference's EMACallback); load it with weights='model'")
+
+
 def load_checkpoint(path: str, device: torch.device = torch.device("cuda"),
-                    overrides: Optional[dict] = None) -> Tuple[EGNNDynamics, dict]:
+                    overrides: Optional[dict] = None, weights: str = "model") -> Tuple[EGNNDynamics, dict]:
     """`DDPMModule.load_from_checkpoint(path).ddpm.dynamics` (demo.py:269) for the MI355X backend: reads the file with the
-    restricted unpickler and builds `EGNNDynamics` with the checkpoint's weights (strict).  Returns (dynamics, hyper_parameters)."""
+    restricted unpickler and builds `EGNNDynamics` with the checkpoint's weights (strict).  Returns (dynamics, hyper_parameters).
+    `weights="ema"`: the averaged weights the reference's `EMACallback` stored with the file (`ema_state_from_checkpoint`) instead of
+    the model's own - same prefix, same strict load; a file without them raises KeyError."""
+    if weights not in ("model", "ema"):
+        raise ValueError("weights must be 'model' or 'ema'")
     ckpt = dict(read_checkpoint(path))
     ckpt["hyper_parameters"] = _plain(ckpt.get("hyper_parameters", {}))
+    if weights == "ema":
+        ckpt["state_dict"] = ema_state_from_checkpoint(ckpt)
     return dynamics_from_checkpoint(ckpt, device=device, overrides=overrides)
 
 

@@ -27,7 +27,7 @@
 #include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
-#define OARD_VERSION 2040      // round 6: + oard_graph_* (general edge lists), oard_library_stream
+#define OARD_VERSION 2041      // + oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update (2040: oard_graph_*, oard_library_stream)
 // The first-generation kernels (weights straight from L2, one wave per 16 nodes: gcl_variant / equi_variant / node_variant 0) are the
 // A/B baseline of round 1 and a cross-check in tests/test_hip_parity.py::test_every_kernel_variant_is_parity_green; they are compiled
 // into experiment builds (-DOARD_EXPERIMENTS) only - a product library refuses those variants (oard_debug_option returns OARD_EINVAL).
@@ -2336,6 +2336,46 @@ int oard_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* 
     if (n > 0)
         LAUNCH(F_OTHER, k_adamw_dev, cdiv(n, 256), 256, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, (long long)n, amsgrad,
                reinterpret_cast<const AdamScal*>(clip_state + 4 + capacity));
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+// ---- the same two steps with the weights' exponential moving average folded in, and the average alone (trainer/ema.py:37-47) ----------
+static bool ema_args_ok(const float* ema, double ema_decay) { return ema && ema_decay >= 0.0 && ema_decay <= 1.0; }      // NaN fails both
+
+int oard_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, double lr,
+                        double beta1, double beta2, double eps, double weight_decay, int64_t step, int amsgrad, double grad_scale,
+                        float* ema, double ema_decay, oard_stream_t stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || n < 0 || step < 1 || !ema_args_ok(ema, ema_decay))
+        return OARD_EINVAL;
+    if (n == 0) return OARD_OK;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    LAUNCH(F_OTHER, k_adamw_ema, cdiv(n, 256), 256, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, (long long)n,
+           (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(lr / bc1),
+           (float)(1.0 / sqrt(bc2)), amsgrad, (float)grad_scale, ema, (float)ema_decay, (float)(1.0 - ema_decay));
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+int oard_adamw_step_dev_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, double lr,
+                            double beta1, double beta2, double eps, double weight_decay, int amsgrad, int clip, double* clip_state,
+                            int capacity, const float* grad_norm, const float* flag, float* out4, float* ema, double ema_decay,
+                            oard_stream_t stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || n < 0 || !clip_state || capacity < 1 || capacity > 64 ||
+        !grad_norm || !flag || !out4 || !ema_args_ok(ema, ema_decay))
+        return OARD_EINVAL;
+    LAUNCH(F_OTHER, k_clip_decide, 1, 64, (hipStream_t)stream, clip_state, capacity, grad_norm, flag, clip, lr, beta1, beta2, eps, weight_decay, out4);
+    if (n > 0)
+        LAUNCH(F_OTHER, k_adamw_dev_ema, cdiv(n, 256), 256, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, (long long)n,
+               amsgrad, reinterpret_cast<const AdamScal*>(clip_state + 4 + capacity), ema, (float)ema_decay, (float)(1.0 - ema_decay));
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+int oard_ema_update(float* ema, const float* param, int64_t n, double ema_decay, oard_stream_t stream) {
+    if (!param || n < 0 || !ema_args_ok(ema, ema_decay)) return OARD_EINVAL;
+    if (n == 0) return OARD_OK;
+    LAUNCH(F_OTHER, k_ema_update, cdiv(n, 256), 256, (hipStream_t)stream, ema, param, (long long)n, (float)ema_decay, (float)(1.0 - ema_decay));
     HIP_TRY(hipGetLastError());
     return OARD_OK;
 }

@@ -241,3 +241,58 @@ OARD_KERNEL __global__ void k_adamw_dev(float* __restrict__ p, const float* __re
     else den = sqrtf(vi) * sc->inv_bc2s + sc->eps;
     p[i] = x - sc->step_size * (mi / den);
 }
+
+// ---- exponential moving average of the weights (trainer/ema.py:37-47: timm's ModelEmaV2.update after every batch) ------------------------
+// ema = fl(fl(d ema) + fl(w p)), d = float32(decay), w = float32(1 - decay) (subtracted in double on the host, rounded once): two rounded
+// products and one add, which is what torch evaluates for `decay * e + (1. - decay) * m` on float32 tensors - hence no contraction here.
+OARD_DEV float ema_mix(float e, float p, float d, float w) {
+#pragma clang fp contract(off)
+    const float a = d * e;
+    const float b = w * p;
+    return a + b;
+}
+
+// the EMA line alone: the generic (autograd + torch.optim.AdamW) step, and callers that step the weights themselves
+OARD_KERNEL __global__ void k_ema_update(float* __restrict__ ema, const float* __restrict__ p, long long n, float d, float w) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    ema[i] = ema_mix(ema[i], p[i], d, w);
+}
+
+// k_adamw with the EMA line on the fresh parameter while it is still in a register: no launch, one more read and write of the bucket
+OARD_KERNEL __global__ void k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            float* __restrict__ vmax, long long n, float decay, float w1, float beta2, float w2, float eps, float step_size,
+                            float inv_bc2s, int amsgrad, float gscale, float* __restrict__ ema, float ema_d, float ema_w) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float gr = g[i] * gscale;
+    const float x = p[i] * decay;
+    const float mi = m[i] + w1 * (gr - m[i]);
+    const float vi = v[i] * beta2 + w2 * (gr * gr);
+    m[i] = mi; v[i] = vi;
+    float den;
+    if (amsgrad) { const float vm = fmaxf(vmax[i], vi); vmax[i] = vm; den = sqrtf(vm) * inv_bc2s + eps; }
+    else den = sqrtf(vi) * inv_bc2s + eps;
+    const float pn = x - step_size * (mi / den);
+    p[i] = pn;
+    ema[i] = ema_mix(ema[i], pn, ema_d, ema_w);
+}
+
+// k_adamw_dev likewise; a skipped step touches neither the weights nor their average
+OARD_KERNEL __global__ void k_adamw_dev_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ vmax, long long n, int amsgrad, const AdamScal* __restrict__ sc,
+                                float* __restrict__ ema, float ema_d, float ema_w) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || sc->skip) return;
+    const float gr = g[i] * sc->gscale;
+    const float x = p[i] * sc->decay;
+    const float mi = m[i] + sc->w1 * (gr - m[i]);
+    const float vi = v[i] * sc->beta2 + sc->w2 * (gr * gr);
+    m[i] = mi; v[i] = vi;
+    float den;
+    if (amsgrad) { const float vm = fmaxf(vmax[i], vi); vmax[i] = vm; den = sqrtf(vm) * sc->inv_bc2s + sc->eps; }
+    else den = sqrtf(vi) * sc->inv_bc2s + sc->eps;
+    const float pn = x - sc->step_size * (mi / den);
+    p[i] = pn;
+    ema[i] = ema_mix(ema[i], pn, ema_d, ema_w);
+}

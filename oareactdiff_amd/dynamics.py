@@ -137,6 +137,11 @@ class EGNNDynamics(nn.Module):
         if "in_edge_nf" in model_config:
             raise NotImplementedError("edge attributes are not part of the LEFTNet denoising path")
         model_config.setdefault("in_hidden_channels", 8)
+        #: what builds a second module of this configuration (DDPMTrainer.ema_dynamics): no `source`, no device - its tensors are the caller's
+        self._ctor_args = dict(model_config=dict(model_config), fragment_names=list(fragment_names), node_nfs=list(node_nfs), edge_nf=edge_nf,
+                               condition_nf=condition_nf, pos_dim=pos_dim, update_pocket_coords=update_pocket_coords,
+                               condition_time=condition_time, edge_cutoff=edge_cutoff, model=model,
+                               enforce_same_encoding=None if enforce_same_encoding is None else list(enforce_same_encoding))
         self.model_config = model_config
         self.node_nfs = node_nfs
         self.edge_nf = edge_nf

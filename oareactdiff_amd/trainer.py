@@ -24,6 +24,8 @@ import copy
 import ctypes as C
 import math
 import os
+import warnings
+from collections import OrderedDict
 from collections.abc import Mapping
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -102,8 +104,19 @@ class DDPMTrainer:
                  scales: Sequence[float] = (1.0, 1.0, 1.0), fixed_idx: Optional[List[int]] = None,
                  optimizer_config: Optional[Dict] = None, clip_grad: bool = True,
                  process_group: Optional["dist.ProcessGroup"] = None, fused: Optional[bool] = None, host_sync: bool = True,
-                 microbatches: int = 1):
-        """`microbatches=2` (fused steps on batches that carry their host copies, `to_device`): the step's reactions are dealt to two
+                 microbatches: int = 1, ema_decay: Optional[float] = None):
+        """`ema_decay=d` (0 <= d <= 1; None: no average, no buffer): an exponential moving average of the trainable weights, updated
+        after every optimiser step that is taken - what the reference wires as `EMACallback` (trainer/train_ts1x.py:188-189,
+        trainer/ema.py:37-47: timm's `ModelEmaV2.update` after every batch), in float32:
+            ema = fl(fl(d32 * ema) + fl(w32 * p_new)),   d32 = float32(d), w32 = float32(1.0 - d)
+        i.e. bit for bit torch's `decay * e + (1. - decay) * m`.  It starts as a copy of the weights (after `sync_replicas`), lives in ONE
+        flat buffer `flat_ema` laid out like the gradient bucket, and a skipped step leaves it untouched.  The fused step folds the line
+        into the AdamW kernel (`oard_adamw_step_ema` / `oard_adamw_step_dev_ema`: no extra launch); the generic step evaluates the same
+        expression per tensor.  NAMING: `d` is timm's decay, the weight of the OLD average.  The reference's `EMACallback(decay=x)` hands
+        `1 - x` to timm (ema.py:29) and train_ts1x.py passes `ema_decay=0.999` into it - to reproduce that callback pass `1 - x` here.
+        Use the average through `ema_dynamics`, `ema_state_dict()`, `compute_loss(..., weights="ema")` and `copy_ema_to_model()`.
+
+        `microbatches=2` (fused steps on batches that carry their host copies, `to_device`): the step's reactions are dealt to two
         halves that run their forward and their reverse sweep CONCURRENTLY on two streams (the caller's and the library's idle
         sub-batch stream), each with its own tape / workspace / scratch and its own gradient buffer, summed before the all-reduce.
         Same loss, same gradient up to the order of one addition; the low-occupancy node-side launches of one half then run beside
@@ -144,6 +157,13 @@ class DDPMTrainer:
         self._bucket = torch.zeros(n + 1, dtype=self.params[0].dtype, device=self.params[0].device)
         self.flat_grad = self._bucket[:n]
         self.skipped_steps = 0
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1] (got {ema_decay!r})")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.flat_ema: Optional[Tensor] = None
+        self._ema_dynamics = None                      # the shadow module, built at the first look at `ema_dynamics`
+        self._ema_warned = False
+        self._ema_view_list = None
         if self.collectives:
             self.sync_replicas()
         off = 0
@@ -175,6 +195,8 @@ class DDPMTrainer:
             self.exp_avg_sq = torch.zeros_like(self.flat_param)
             self.max_exp_avg_sq = torch.zeros_like(self.flat_param)
             self.opt_step = 0
+        if self.ema_decay is not None:                 # ModelEmaV2.__init__: a copy of the weights (the replicas are synchronised by now)
+            self.flat_ema = self._flat_weights()
         # `trainer.optimizer` is what the reference's configure_optimizers returns (pl_trainer.py:149-151): the generic path steps it;
         # the fused path runs oard_adamw_step on the flat buffers but reads lr / betas / eps / weight_decay / amsgrad from
         # `optimizer.param_groups[0]` at EVERY step, so an LR scheduler attached to it (or an edit of the group) takes effect in
@@ -202,6 +224,9 @@ class DDPMTrainer:
                 sd[k] = getattr(self, k).detach().clone()
         else:
             sd["optimizer"] = copy.deepcopy(self.optimizer.state_dict())     # a snapshot: torch hands out the live moment tensors
+        if self.flat_ema is not None:                  # (no key at all without EMA: states of earlier versions and of EMA-less runs are the same)
+            sd["ema_decay"] = float(self.ema_decay)
+            sd["ema"] = self.flat_ema.detach().clone()
         return sd
 
     def load_state_dict(self, sd: Dict) -> None:
@@ -222,6 +247,18 @@ class DDPMTrainer:
                     getattr(self, k).copy_(sd[k].to(self.flat_param.device))
         else:
             self.optimizer.load_state_dict(sd["optimizer"])
+        if self.flat_ema is not None:                  # (a saved average is ignored by a trainer that keeps none)
+            with torch.no_grad():
+                if sd.get("ema") is not None:
+                    self.ema_decay = float(sd.get("ema_decay", self.ema_decay))
+                    self.flat_ema.copy_(sd["ema"].to(device=self.flat_ema.device, dtype=self.flat_ema.dtype))
+                else:                                  # the run that wrote this state kept no average: start one from the weights it resumes
+                    if not self._ema_warned:
+                        self._ema_warned = True
+                        warnings.warn("trainer state holds no EMA: the average restarts from the current weights")
+                    self.flat_ema.copy_(self._flat_weights())
+            if self._ema_dynamics is not None:
+                self._ema_dynamics.invalidate_packed()
 
     # ---- host_sync=False: history / step counter / skip counter live on the device between reads ------------------------------------------
     CLIP_CAPACITY = 50                                 # utils/training_tools.py:9 (Queue(max_len=50))
@@ -262,9 +299,138 @@ class DDPMTrainer:
         return out, (cond.to(device, non_blocking=non_blocking) if isinstance(cond, Tensor) else cond)
 
     # pl_trainer.py:208-282
-    def compute_loss(self, batch, training: bool = True, **kw) -> Tuple[Tensor, Dict[str, float]]:
+    def compute_loss(self, batch, training: bool = True, weights: str = "live", **kw) -> Tuple[Tensor, Dict[str, float]]:
+        """`weights="ema"` (evaluation only): the loss under the averaged weights, through `ema_dynamics` - the reference's validation
+        under EMA weights (ema.py:49-60) without its store / copy / restore of the live ones."""
         representations, conditions = batch
-        return self.loss.compute_loss(representations, conditions, training=training, **kw)
+        if weights == "live":
+            return self.loss.compute_loss(representations, conditions, training=training, **kw)
+        if weights != "ema":
+            raise ValueError("weights must be 'live' or 'ema'")
+        if training:
+            raise ValueError("weights='ema' evaluates (training=False): the average is not what the optimiser steps")
+        self.loss.dynamics = self.ema_dynamics
+        try:
+            with torch.no_grad():
+                return self.loss.compute_loss(representations, conditions, training=False, **kw)
+        finally:
+            self.loss.dynamics = self.dynamics
+
+    # ---- the moving average of the weights (trainer/ema.py; see `ema_decay` in __init__) ---------------------------------------------------
+    def _flat_weights(self) -> Tensor:
+        """A fresh flat copy of the trainable weights in the bucket's order."""
+        if self.fused:
+            return self.flat_param.detach().clone()
+        return torch.cat([p.detach().reshape(-1) for p in self.params])
+
+    def _need_ema(self) -> Tensor:
+        if self.flat_ema is None:
+            raise RuntimeError("this trainer keeps no EMA of the weights (DDPMTrainer(ema_decay=...))")
+        return self.flat_ema
+
+    def _ema_views(self) -> List[Tensor]:
+        """`flat_ema` as one view per trainable tensor (made once: the buffer is only ever written in place)."""
+        if self._ema_view_list is None:
+            views, off = [], 0
+            for p in self.params:
+                views.append(self.flat_ema[off: off + p.numel()].view_as(p))
+                off += p.numel()
+            self._ema_view_list = views
+        return self._ema_view_list
+
+    def _ema_step_generic(self) -> None:
+        """The generic step's update, after `optimizer.step()`.  float32 weights on a ROCm device: `oard_ema_update` on views of the flat
+        average that copy nothing - ONE call where the weights are one flat buffer too (a fused trainer stepped with `generic=True`), one
+        per tensor otherwise (the generic trainer's parameters are not views of one buffer).  Anywhere else (CPU, other dtypes):
+        `ModelEmaV2.update`'s expression per tensor as a `mul_` / `add_` pair with the two float32 scalars - the same bits."""
+        d = float(np.float32(self.ema_decay))
+        w = float(np.float32(1.0 - self.ema_decay))
+        ema = self.flat_ema
+        with torch.no_grad():
+            if ema.is_cuda and ema.dtype == torch.float32:
+                L = _capi.lib()
+                stream = torch.cuda.current_stream(ema.device).cuda_stream
+                pairs = [(ema, self.flat_param)] if self.fused else zip(self._ema_views(), self.params)
+                with torch.cuda.device(ema.device):
+                    for e, p in pairs:
+                        if not p.is_contiguous():
+                            raise _capi.OardError("the EMA update needs contiguous parameters")
+                        _capi.check(L.oard_ema_update(e.data_ptr(), p.data_ptr(), p.numel(), self.ema_decay, stream), "oard_ema_update")
+            else:
+                for e, p in zip(self._ema_views(), self.params):
+                    e.mul_(d).add_(p.detach() * w)
+        if self._ema_dynamics is not None:
+            self._ema_dynamics.invalidate_packed()
+
+    def ema_state_dict(self) -> "OrderedDict[str, Tensor]":
+        """The module's `state_dict()` with the averaged tensors in place of the trainable ones (copies; buffers and the parameters the
+        forward never uses equal their average).  Names and shapes are the reference's: it loads with strict=True into the reference's
+        EGNNDynamics or into a fresh one here."""
+        ema = self._need_ema()
+        where, off = {}, 0
+        for p in self.params:
+            where[id(p)] = off
+            off += p.numel()
+        out = OrderedDict()
+        for name, t in self.dynamics.state_dict(keep_vars=True).items():
+            o = where.get(id(t))
+            out[name] = (t.detach() if o is None else ema[o: o + t.numel()].view_as(t)).clone()
+        return out
+
+    def copy_ema_to_model(self) -> None:
+        """The averaged weights become the model's (EMACallback.on_train_end, ema.py:62-65): one device-to-device copy of the flat buffer,
+        or one copy per tensor on the generic path."""
+        ema = self._need_ema()
+        with torch.no_grad():
+            if self.fused:
+                self.flat_param.copy_(ema)
+            else:
+                for e, p in zip(self._ema_views(), self.params):
+                    p.copy_(e)
+        if hasattr(self.dynamics, "invalidate_packed"):
+            self.dynamics.invalidate_packed()
+
+    @property
+    def ema_dynamics(self) -> nn.Module:
+        """A second module of the live one's class and configuration whose trainable parameters are VIEWS into `flat_ema`; every other
+        tensor (buffers, the parameters the forward never uses) shares storage with the live module's.  Built at the first look from the
+        live module's constructor arguments; its per-call buffers and its packed weights are its own and appear at its first call, so
+        nothing is allocated for a run that never samples from the average.  Hand it to `DiffusionSampler`, `inpaint` or
+        `compute_loss(weights="ema")` while training continues: no copy is made, the live weights and their packed blob are not touched,
+        and every taken step marks its packed weights stale, so that its next call repacks them.  requires_grad is False throughout;
+        `edge_precision` and `nan_check` are the live module's at the time it is built.
+        Like any module it serves one stream at a time, and `flat_ema` is written on the stream the training step runs on: a caller
+        on another stream orders itself behind the step (`stream.wait_stream(...)`) before it calls the shadow."""
+        if self._ema_dynamics is None:
+            ema = self._need_ema()
+            live = self.dynamics
+            args = getattr(live, "_ctor_args", None)
+            if args is None:
+                raise RuntimeError("ema_dynamics needs a module that keeps its constructor arguments (oareactdiff_amd.EGNNDynamics)")
+            args = dict(args, model_config=dict(args["model_config"]), device=torch.device("meta"))     # nothing allocated: every tensor is replaced
+            shadow = type(live)(**args)
+            shadow.device = live.device
+            where, off = {}, 0
+            for p in self.params:
+                where[id(p)] = off
+                off += p.numel()
+            made: Dict[int, Tensor] = {}
+            shadow._ordered_tensors()                  # resolves the (owning module, attribute) pair of every state-dict entry
+            for (mod, attr), t in zip(shadow._slots[1], live._ordered_tensors()):
+                new = made.get(id(t))
+                if new is None:
+                    o = where.get(id(t))
+                    data = t.detach() if o is None else ema[o: o + t.numel()].view_as(t)
+                    new = made[id(t)] = nn.Parameter(data, requires_grad=False) if isinstance(t, nn.Parameter) else data
+                if attr in mod._parameters:
+                    mod._parameters[attr] = new
+                else:
+                    mod._buffers[attr] = new
+            shadow.edge_precision, shadow.train_edge_precision = live.edge_precision, live.train_edge_precision
+            shadow.nan_check, shadow.edge_list_path = live.nan_check, live.edge_list_path
+            shadow.eval()
+            self._ema_dynamics = shadow
+        return self._ema_dynamics
 
     def sync_replicas(self, check: bool = True) -> None:
         """What torch DDP does when it wraps a module (Lightning `DDPStrategy`, train_ts1x.py:197-203): rank 0's parameters
@@ -294,6 +460,17 @@ class DDPMTrainer:
                     dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=self.group)
                     dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=self.group)
                     assert float(lo) == float(hi), "replicas differ after the initial broadcast"
+            if self.flat_ema is not None:                  # the average travels with the weights (at construction it does not exist yet:
+                src = dist.get_global_rank(self.group, 0) if self.group is not None else 0      # it is then copied from the synchronised ones)
+                dist.broadcast(self.flat_ema, src=src, group=self.group)
+                if self._ema_dynamics is not None:
+                    self._ema_dynamics.invalidate_packed()
+                if check:
+                    cs = self.flat_ema.double().abs().sum().reshape(1)
+                    lo, hi = cs.clone(), cs.clone()
+                    dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=self.group)
+                    dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=self.group)
+                    assert float(lo) == float(hi), "EMA buffers differ after the broadcast"
 
     def all_reduce_gradients(self) -> None:
         """DDP's gradient averaging as one collective over the flat bucket (sum, then / world).  The last element of the
@@ -513,14 +690,20 @@ class DDPMTrainer:
             out4 = torch.empty(4, dtype=torch.float32, device=stats_dev.device)
             o = self.optimizer.param_groups[0]
             stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
-            with torch.cuda.device(self.flat_grad.device):
-                _capi.check(_capi.lib().oard_adamw_step_dev(
-                    self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+            args = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
                     self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(), float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]),
                     float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), 1 if o.get("amsgrad", False) else 0,
                     1 if self.clip_grad else 0, state.data_ptr(), self.CLIP_CAPACITY, stats_dev.data_ptr(),
-                    stats_dev.data_ptr() + 4, out4.data_ptr(), stream), "oard_adamw_step_dev")
+                    stats_dev.data_ptr() + 4, out4.data_ptr())
+            with torch.cuda.device(self.flat_grad.device):
+                if self.flat_ema is None:
+                    _capi.check(_capi.lib().oard_adamw_step_dev(*args, stream), "oard_adamw_step_dev")
+                else:                                 # the same two launches, the average updated by the AdamW kernel (not at all if skipped)
+                    _capi.check(_capi.lib().oard_adamw_step_dev_ema(*args, self.flat_ema.data_ptr(), self.ema_decay, stream),
+                                "oard_adamw_step_dev_ema")
             dyn.invalidate_packed()                   # the weights changed (unless the step was skipped: repacking is harmless)
+            if self._ema_dynamics is not None:
+                self._ema_dynamics.invalidate_packed()
             return LazyInfo(stats_dev, out4, K, [float(x) for x in self.loss.scales], self.clip_grad)
         if self._clip_state is not None:               # host_sync was switched on again: the host copies become the truth
             self._pull_clip_state()
@@ -552,13 +735,18 @@ class DDPMTrainer:
             o = self.optimizer.param_groups[0]
             self.opt_step += 1
             stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
+            args = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                    self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(), float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]),
+                    float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), self.opt_step, 1 if o.get("amsgrad", False) else 0,
+                    float(gscale))
             with torch.cuda.device(self.flat_grad.device):
-                _capi.check(_capi.lib().oard_adamw_step(self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(),
-                                                        self.exp_avg_sq.data_ptr(), self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(),
-                                                        float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]), float(o.get("eps", 1e-8)),
-                                                        float(o.get("weight_decay", 0.0)), self.opt_step, 1 if o.get("amsgrad", False) else 0,
-                                                        float(gscale), stream), "oard_adamw_step")
+                if self.flat_ema is None:
+                    _capi.check(_capi.lib().oard_adamw_step(*args, stream), "oard_adamw_step")
+                else:
+                    _capi.check(_capi.lib().oard_adamw_step_ema(*args, self.flat_ema.data_ptr(), self.ema_decay, stream), "oard_adamw_step_ema")
             dyn.invalidate_packed()                   # the weights changed behind torch's version counters
+            if self._ema_dynamics is not None:
+                self._ema_dynamics.invalidate_packed()
         info["loss"] = stats[2]
         info["skipped"] = int(skipped)
         return info
@@ -612,6 +800,8 @@ class DDPMTrainer:
             if self.clip_grad:
                 info["grad_norm"], info["max_grad_norm"] = self.clip_gradients(grad_norm)
             self.optimizer.step()
+            if self.flat_ema is not None:
+                self._ema_step_generic()
         info["loss"] = loss_value
         info["skipped"] = int(skipped)
         return {k: (float(v) if isinstance(v, Tensor) else v) for k, v in info.items()}
