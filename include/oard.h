@@ -481,7 +481,31 @@ int oard_adamw_step_dev_ema(float* param_dev, const float* grad_dev, float* exp_
                             float* ema_dev, double ema_decay, oard_stream_t stream);
 int oard_ema_update(float* ema_dev, const float* param_dev, int64_t n, double ema_decay, oard_stream_t stream);
 
-/* The library's own streams of the current device (three non-blocking streams, chosen once per device so that each runs on a hardware
+/* ---- validation metric: optimal-superposition RMSD per molecule ------------------------------------------------------------------
+ * Replaces: the same-order Kabsch fit of rmsd_core (oa_reactdiff/analyze/rmsd.py:30-35, pymatgen's KabschMatcher), the chirality
+ * handling of pymatgen_rmsd and the per-molecule loop of batch_rmsd (:54-100), which DDPMModule.eval_inplaint_batch logs
+ * (trainer/pl_trainer.py:284-325).  NOT replaced: the permutation search over like atoms of rmsd_core's other branch (:36-51) - rows
+ * are compared in the order given, an upper bound on the order-matched number.
+ * Segment g is rows seg_ptr[g] .. seg_ptr[g + 1] (seg_ptr_dev: n_segments + 1 ascending int32) of a_dev and b_dev: row-major float32
+ * with row strides lda / ldb >= 3 in ELEMENTS, coordinates in the first three columns (the other columns are never read, so the
+ * [n, node_nf] tensors of the samplers are passed as they are).  One wavefront per segment (csrc/oard_kabsch.h); float64 throughout:
+ * fixed-order sums (bitwise reproducible, independent of the other segments of the launch), Horn's quaternion matrix diagonalised by
+ * cyclic Jacobi (n = 1, 2, collinear, coplanar and identical structures included), the RMSD as the residual of a second pass,
+ *     rmsd[g] = sqrt(sum_rows |R (b - c_b) - (a - c_a)|^2 / n),     R the proper rotation minimising it.
+ * flags bit 0 (allow reflection, the reference's ignore_chirality=True): the fit is repeated with the z column of the centred b negated
+ * and the smaller RMSD kept, with its improper map.  cap > 0: rmsd = min(rmsd, cap) (the reference's min(rmsd, 1.0)).
+ * An empty segment gives NaN; a segment with a non-finite coordinate gives cap if cap > 0, else NaN (the reference's `except: 1.0`);
+ * their rot / aligned entries are NaN.
+ * rot_dev (or NULL): [n_segments, 9] row-major 3 x 3, the map taking centred b onto centred a (reflection folded in when chosen).
+ * aligned_dev (or NULL): [rows, 3], row r = rot (b_r - c_b) + c_a with rot as returned (rounded to float32): b in a's frame.
+ * OARD_EINVAL for null a / b / seg_ptr / rmsd, n_segments < 0, lda < 3 or ldb < 3; n_segments == 0 returns OARD_OK without a launch.
+ * Needs no oard_config and no topology (production and general path alike); no allocation, asynchronous on `stream`, capturable. */
+int oard_kabsch_rmsd(const float* a_dev, int64_t lda, const float* b_dev, int64_t ldb,
+                     const int32_t* seg_ptr_dev, int64_t n_segments, int flags /* bit 0: allow reflection */,
+                     float cap /* <= 0: none */, float* rmsd_dev, float* rot_dev /* or NULL */,
+                     float* aligned_dev /* or NULL */, oard_stream_t stream);
+
+/* The library's own streams of the current device(three non-blocking streams, chosen once per device so that each runs on a hardware
  * queue of its own beside the caller's stream - the runtime serves a process's streams from 4 queues): 0 = the training sweep's
  * gradient stream (and the second sub-batch of a multi-part forward), 1 = the third sub-batch, 2 = topology uploads (and the fourth).
  * For callers that want a second in-order queue WITHOUT adding a fifth stream to the process: DDPMTrainer's two-micro-batch step runs

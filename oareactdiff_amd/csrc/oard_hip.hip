@@ -27,7 +27,7 @@
 #include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
-#define OARD_VERSION 2041      // + oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update (2040: oard_graph_*, oard_library_stream)
+#define OARD_VERSION 2042      // + oard_kabsch_rmsd (2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
 // The first-generation kernels (weights straight from L2, one wave per 16 nodes: gcl_variant / equi_variant / node_variant 0) are the
 // A/B baseline of round 1 and a cross-check in tests/test_hip_parity.py::test_every_kernel_variant_is_parity_green; they are compiled
 // into experiment builds (-DOARD_EXPERIMENTS) only - a product library refuses those variants (oard_debug_option returns OARD_EINVAL).
@@ -2151,6 +2151,7 @@ int oard_wgrad(const float* dY, int ldY, int ncY, int o_len, int o_pad, int MO, 
 }  // extern "C"
 #include "oard_train_stages.h"
 #include "oard_loss.h"
+#include "oard_kabsch.h"     // k_kabsch_rmsd: the validation metric (oard_kabsch_rmsd)
 extern "C" {
 
 // ---- the backward sweep through the C ABI (include/oard.h) ------------------------------------------------------------------------
@@ -2376,6 +2377,17 @@ int oard_ema_update(float* ema, const float* param, int64_t n, double ema_decay,
     if (!param || n < 0 || !ema_args_ok(ema, ema_decay)) return OARD_EINVAL;
     if (n == 0) return OARD_OK;
     LAUNCH(F_OTHER, k_ema_update, cdiv(n, 256), 256, (hipStream_t)stream, ema, param, (long long)n, (float)ema_decay, (float)(1.0 - ema_decay));
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+// ---- the validation metric: optimal-superposition RMSD per segment (analyze/rmsd.py:30-35, 54-100; oard_kabsch.h) -------------------------
+int oard_kabsch_rmsd(const float* a, int64_t lda, const float* b, int64_t ldb, const int32_t* seg_ptr, int64_t n_segments, int flags,
+                     float cap, float* rmsd, float* rot, float* aligned, oard_stream_t stream) {
+    if (!a || !b || !seg_ptr || !rmsd || n_segments < 0 || n_segments > 0x7fffffffLL || lda < 3 || ldb < 3) return OARD_EINVAL;
+    if (n_segments == 0) return OARD_OK;
+    LAUNCH(F_OTHER, k_kabsch_rmsd, n_segments, 64, (hipStream_t)stream, a, (long long)lda, b, (long long)ldb, seg_ptr, flags, cap, rmsd, rot,
+           aligned);
     HIP_TRY(hipGetLastError());
     return OARD_OK;
 }

@@ -136,6 +136,10 @@ class DDPMTrainer:
         self.loss = DiffusionLoss(dynamics, noise_schedule, timesteps, precision, norm_values=norm_values,
                                   norm_biases=norm_biases, pos_only=pos_only, fixed_idx=fixed_idx, loss_type=loss_type,
                                   scales=scales)
+        # what a DiffusionSampler of this model needs besides the schedule (eval_inpaint_batch builds one per schedule / weights, lazily)
+        self._sampler_kw = dict(precision=precision, pos_only=pos_only, norm_values=tuple(norm_values), norm_biases=tuple(norm_biases))
+        self._eval_samplers: Dict[Tuple[str, int, str], object] = {}
+        self.last_rmsds: Optional[Tensor] = None        # per-reaction RMSDs of the last eval_inpaint_batch (device, [B])
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         self.time_collectives = False                      # True: all_reduce_gradients brackets the collective with timing events (collective_report)
@@ -315,6 +319,59 @@ class DDPMTrainer:
                 return self.loss.compute_loss(representations, conditions, training=False, **kw)
         finally:
             self.loss.dynamics = self.dynamics
+
+    # pl_trainer.py:284-325
+    def eval_inpaint_batch(self, batch, resamplings: int = 5, jump_length: int = 5, frag_fixed: Sequence[int] = (0, 2), idx: int = 1,
+                           weights: str = "live", noise_schedule: str = "polynomial_2", timesteps: Optional[int] = None,
+                           cap: Optional[float] = 1.0, noise_fn=None) -> Tuple[float, float]:
+        """The validation metric of the reference's `eval_inplaint_batch` (pl_trainer.py:284-325, logged by training_step / _shared_eval):
+        object `idx` (the transition state) of every reaction of `batch` is inpainted with the objects `frag_fixed` (reactant, product)
+        held fixed, and the (mean, median) RMSD between the generated and the true structure is returned.
+            xh_fixed = cat(pos, one_hot, charge) per object;  fragments_nodes = the batch's `size` tensors
+            out_samples, _ = DiffusionSampler.inpaint(...)           the fused RePaint loop (sampler.py)
+            rmsds = metrics.batch_rmsd(fragments_nodes, out_samples[0], xh_fixed, idx, cap=cap)      one launch, one wavefront per reaction
+        `noise_schedule` / `timesteps` stand for the reference's separate `sampling_schedule` (None: the trainer's own timesteps); the
+        sampler is built once per (noise_schedule, timesteps, weights) and reused.  `weights="ema"` samples through `ema_dynamics`: no
+        weight is copied in either direction (the reference swaps a snapshot in and out, ema.py:49-60).  `cap` is `batch_rmsd`'s: 1.0 as in
+        the reference, None for the uncapped numbers; a reaction whose sample is not finite counts `cap` (None: it is left out).
+        Mean and median are taken on the device over the finite entries, the median as numpy's (the mean of the two middle values of an
+        even count); no finite entry gives (nan, nan).  The per-reaction tensor stays in `self.last_rmsds` ([B], device).
+        Host reads: the loop's NaN flag and the two returned scalars - given a batch that carries `size_host` (`to_device`); the batch
+        layout is otherwise read from the device `size` tensors once per new layout.  A NaN network output does not raise: the loop
+        warns, and the affected reactions are the non-finite ones above.
+        The call changes no weight, no optimiser or EMA state, and neither the module's `training` flag nor its `nan_check`.
+        RMSD as in `oareactdiff_amd.metrics`: atoms matched in the order given - the reference's permutation search is not implemented."""
+        from .metrics import batch_rmsd
+        from .sampler import DiffusionSampler
+        if weights not in ("live", "ema"):
+            raise ValueError("weights must be 'live' or 'ema'")
+        T = int(self.loss.T if timesteps is None else timesteps)
+        key = (str(noise_schedule), T, weights)
+        smp = self._eval_samplers.get(key)
+        if smp is None:
+            dyn = self.dynamics if weights == "live" else self.ema_dynamics
+            smp = self._eval_samplers[key] = DiffusionSampler(dyn, noise_schedule, T, on_nan="warn", **self._sampler_kw)
+        representations, conditions = batch
+        xh_fixed = [torch.cat([r["pos"], r["one_hot"], r["charge"]], dim=1) for r in representations]
+        fragments_nodes = [r["size"] for r in representations]
+        n_samples = int(fragments_nodes[0].numel())
+        out_samples, _ = smp.inpaint(n_samples, [r.get("size_host", r["size"]) for r in representations], conditions=conditions,
+                                     return_frames=1, resamplings=resamplings, jump_length=jump_length, timesteps=None,
+                                     xh_fixed=xh_fixed, frag_fixed=list(frag_fixed), noise_fn=noise_fn)
+        dev = out_samples[0][idx].device
+        with torch.no_grad():
+            r = batch_rmsd([f.to(dev) for f in fragments_nodes], out_samples[0], [x.to(dev) for x in xh_fixed], idx=idx, cap=cap)
+            self.last_rmsds = r
+            fin = torch.isfinite(r)
+            cnt = fin.sum()
+            r64 = r.double()
+            mean = torch.where(fin, r64, torch.zeros_like(r64)).sum() / cnt                      # 0 / 0 = nan without a finite entry
+            ordered = torch.sort(torch.where(fin, r64, torch.full_like(r64, float("inf")))).values      # the finite ones first
+            mid = torch.stack([(cnt - 1).clamp(min=0) // 2, cnt // 2]).clamp(max=max(n_samples - 1, 0))
+            median = ordered[mid].mean() if n_samples else mean
+            median = torch.where(cnt > 0, median, torch.full_like(median, float("nan")))
+            mean, median = torch.stack([mean, median]).tolist()                                  # the one read of the two scalars
+        return mean, median
 
     # ---- the moving average of the weights (trainer/ema.py; see `ema_decay` in __init__) ---------------------------------------------------
     def _flat_weights(self) -> Tensor:
