@@ -2314,63 +2314,71 @@ int oard_loss_terms(const oard_config* c, const oard_topology* topo, const float
     HIP_TRY(hipGetLastError());
     return OARD_OK;
 }
+// ---- AdamW over the flat bucket, optionally with the weights' exponential moving average folded in (trainer/ema.py:37-47) -------------
+static bool ema_args_ok(const float* ema, double ema_decay) { return ema && ema_decay >= 0.0 && ema_decay <= 1.0; }      // NaN fails both
+
+// what the four entry points share: the buffers of a call and their checks (`with_ema` false: no average, `ema` null)
+struct AdamwCall { float* p; const float* g; float *m, *v, *vmax; int64_t n; int amsgrad; bool with_ema; float* ema; double ema_decay; };
+
+static bool adamw_call_ok(const AdamwCall& c) {
+    return c.p && c.g && c.m && c.v && (!c.amsgrad || c.vmax) && c.n >= 0 && (!c.with_ema || ema_args_ok(c.ema, c.ema_decay));
+}
+
+// the AdamW launch of a checked call with n > 0: the step's scalars by value (`dev` null) or in device memory
+static void adamw_launch(const AdamwCall& c, const AdamScal& host, const AdamScal* dev, hipStream_t stream) {
+    auto kern = dev ? (c.with_ema ? k_adamw<true, true> : k_adamw<true, false>) : (c.with_ema ? k_adamw<false, true> : k_adamw<false, false>);
+    LAUNCH(F_OTHER, kern, cdiv(c.n, 256), 256, stream, c.p, c.g, c.m, c.v, c.vmax, (long long)c.n, c.amsgrad, host, dev, c.ema,
+           (float)c.ema_decay, (float)(1.0 - c.ema_decay));
+}
+
+// the scalars derived on the host, as k_clip_decide derives them on the device
+static int adamw_host_step(const AdamwCall& c, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                           double grad_scale, oard_stream_t stream) {
+    if (!adamw_call_ok(c) || step < 1) return OARD_EINVAL;
+    if (c.n == 0) return OARD_OK;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    AdamScal sc = {};
+    sc.decay = (float)(1.0 - lr * weight_decay); sc.w1 = (float)(1.0 - beta1); sc.beta2 = (float)beta2; sc.w2 = (float)(1.0 - beta2);
+    sc.eps = (float)eps; sc.step_size = (float)(lr / bc1); sc.inv_bc2s = (float)(1.0 / sqrt(bc2)); sc.gscale = (float)grad_scale;
+    adamw_launch(c, sc, nullptr, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+// the clip / skip decision by one device thread, then AdamW on the scalars it left behind the history (n = 0: the decision alone)
+static int adamw_dev_step(const AdamwCall& c, double lr, double beta1, double beta2, double eps, double weight_decay, int clip,
+                          double* clip_state, int capacity, const float* grad_norm, const float* flag, float* out4, oard_stream_t stream) {
+    if (!adamw_call_ok(c) || !clip_state || capacity < 1 || capacity > 64 || !grad_norm || !flag || !out4) return OARD_EINVAL;
+    LAUNCH(F_OTHER, k_clip_decide, 1, 64, (hipStream_t)stream, clip_state, capacity, grad_norm, flag, clip, lr, beta1, beta2, eps, weight_decay, out4);
+    if (c.n > 0) adamw_launch(c, AdamScal{}, reinterpret_cast<const AdamScal*>(clip_state + 4 + capacity), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
 int oard_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, double lr,
                     double beta1, double beta2, double eps, double weight_decay, int64_t step, int amsgrad, double grad_scale,
                     oard_stream_t stream) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || n < 0 || step < 1) return OARD_EINVAL;
-    if (n == 0) return OARD_OK;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    LAUNCH(F_OTHER, k_adamw, cdiv(n, 256), 256, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, (long long)n,
-           (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(lr / bc1),
-           (float)(1.0 / sqrt(bc2)), amsgrad, (float)grad_scale);
-    HIP_TRY(hipGetLastError());
-    return OARD_OK;
+    return adamw_host_step({param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, amsgrad, false, nullptr, 0.0}, lr, beta1, beta2, eps,
+                           weight_decay, step, grad_scale, stream);
 }
-
-int oard_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, double lr,
-                        double beta1, double beta2, double eps, double weight_decay, int amsgrad, int clip, double* clip_state,
-                        int capacity, const float* grad_norm, const float* flag, float* out4, oard_stream_t stream) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || n < 0 || !clip_state || capacity < 1 || capacity > 64 ||
-        !grad_norm || !flag || !out4)
-        return OARD_EINVAL;
-    LAUNCH(F_OTHER, k_clip_decide, 1, 64, (hipStream_t)stream, clip_state, capacity, grad_norm, flag, clip, lr, beta1, beta2, eps, weight_decay, out4);
-    if (n > 0)
-        LAUNCH(F_OTHER, k_adamw_dev, cdiv(n, 256), 256, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, (long long)n, amsgrad,
-               reinterpret_cast<const AdamScal*>(clip_state + 4 + capacity));
-    HIP_TRY(hipGetLastError());
-    return OARD_OK;
-}
-
-// ---- the same two steps with the weights' exponential moving average folded in, and the average alone (trainer/ema.py:37-47) ----------
-static bool ema_args_ok(const float* ema, double ema_decay) { return ema && ema_decay >= 0.0 && ema_decay <= 1.0; }      // NaN fails both
-
 int oard_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, double lr,
                         double beta1, double beta2, double eps, double weight_decay, int64_t step, int amsgrad, double grad_scale,
                         float* ema, double ema_decay, oard_stream_t stream) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || n < 0 || step < 1 || !ema_args_ok(ema, ema_decay))
-        return OARD_EINVAL;
-    if (n == 0) return OARD_OK;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    LAUNCH(F_OTHER, k_adamw_ema, cdiv(n, 256), 256, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, (long long)n,
-           (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(lr / bc1),
-           (float)(1.0 / sqrt(bc2)), amsgrad, (float)grad_scale, ema, (float)ema_decay, (float)(1.0 - ema_decay));
-    HIP_TRY(hipGetLastError());
-    return OARD_OK;
+    return adamw_host_step({param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, amsgrad, true, ema, ema_decay}, lr, beta1, beta2, eps,
+                           weight_decay, step, grad_scale, stream);
 }
-
+int oard_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, double lr,
+                        double beta1, double beta2, double eps, double weight_decay, int amsgrad, int clip, double* clip_state,
+                        int capacity, const float* grad_norm, const float* flag, float* out4, oard_stream_t stream) {
+    return adamw_dev_step({param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, amsgrad, false, nullptr, 0.0}, lr, beta1, beta2, eps,
+                          weight_decay, clip, clip_state, capacity, grad_norm, flag, out4, stream);
+}
 int oard_adamw_step_dev_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n, double lr,
                             double beta1, double beta2, double eps, double weight_decay, int amsgrad, int clip, double* clip_state,
                             int capacity, const float* grad_norm, const float* flag, float* out4, float* ema, double ema_decay,
                             oard_stream_t stream) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || n < 0 || !clip_state || capacity < 1 || capacity > 64 ||
-        !grad_norm || !flag || !out4 || !ema_args_ok(ema, ema_decay))
-        return OARD_EINVAL;
-    LAUNCH(F_OTHER, k_clip_decide, 1, 64, (hipStream_t)stream, clip_state, capacity, grad_norm, flag, clip, lr, beta1, beta2, eps, weight_decay, out4);
-    if (n > 0)
-        LAUNCH(F_OTHER, k_adamw_dev_ema, cdiv(n, 256), 256, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, (long long)n,
-               amsgrad, reinterpret_cast<const AdamScal*>(clip_state + 4 + capacity), ema, (float)ema_decay, (float)(1.0 - ema_decay));
-    HIP_TRY(hipGetLastError());
-    return OARD_OK;
+    return adamw_dev_step({param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, n, amsgrad, true, ema, ema_decay}, lr, beta1, beta2, eps,
+                          weight_decay, clip, clip_state, capacity, grad_norm, flag, out4, stream);
 }
 
 int oard_ema_update(float* ema, const float* param, int64_t n, double ema_decay, oard_stream_t stream) {

@@ -145,23 +145,34 @@ OARD_KERNEL __global__ __launch_bounds__(64) void k_loss_terms(TopoDev tp, LossP
 }
 
 // AdamW (torch.optim.AdamW single-tensor semantics, amsgrad optional) over a flat bucket; `gscale` multiplies the gradient first
-// (clip_grad_norm_'s factor; 1 = no clipping).  Every derived scalar comes from the host in double precision, rounded once, exactly
-// as torch passes its Python-float scalars to the element-wise kernels: decay = 1 - lr wd, w1 = 1 - beta1, w2 = 1 - beta2,
+// (clip_grad_norm_'s factor; 1 = no clipping).  Every derived scalar is computed in double precision and rounded once, exactly as torch
+// passes its Python-float scalars to the element-wise kernels: decay = 1 - lr wd, w1 = 1 - beta1, w2 = 1 - beta2,
 // step_size = lr / (1 - beta1^t), inv_bc2s = 1 / sqrt(1 - beta2^t) (torch divides a tensor by a scalar as a product with its inverse).
-OARD_KERNEL __global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                        float* __restrict__ vmax, long long n, float decay, float w1, float beta2, float w2, float eps, float step_size,
-                        float inv_bc2s, int amsgrad, float gscale) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float gr = g[i] * gscale;
-    const float x = p[i] * decay;
-    const float mi = m[i] + w1 * (gr - m[i]);                             // exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = v[i] * beta2 + w2 * (gr * gr);                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+// The scalars of one step: a kernel argument when the host derives them (oard_adamw_step), in device memory when k_clip_decide does.
+struct AdamScal { float decay, w1, beta2, w2, eps, step_size, inv_bc2s, gscale; int skip; int pad[7]; };
+
+// Element i: its moments (and their running maximum if `amsgrad`) updated in place, the new parameter returned.  The source once read
+//     x = p decay;  m += w1 (g gscale - m);  v = v beta2 + w2 (g gscale)^2;  den = sqrt(v) inv_bc2s + eps;  p = x - step_size (m / den)
+// and left to the compiler which products to fuse into the following sum.  Which ones it fused is part of the result (the last bit
+// of every parameter), and it differed between otherwise identical kernels, so the choice is written out: no contraction here, and
+// an fmaf where the kernels before this function (k_adamw, k_adamw_dev, k_adamw_ema, k_adamw_dev_ema) were compiled to one.  The
+// table records what that build computed, and tests/golden/adamw_bits.npz its bits:
+//     gr      = fl(g gscale)                        rounded; only the square reads it
+//     m       = fma(w1, fma(gscale, g, -m), m)      g gscale unrounded inside the difference; exp_avg.lerp_(grad, 1 - beta1)
+//     v       = fl(fl(v beta2) + fl(w2 fl(gr gr)))  no fusion; exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+//     den     = fma(sqrt(v or vmax), inv_bc2s, eps)
+//     p       = fma(decay, p, -fl(step_size fl(m / den)))      p decay unrounded; param.addcdiv_(exp_avg, denom, value=-step_size)
+OARD_DEV float adamw_elem(float p, float g, float* __restrict__ m, float* __restrict__ v, float* __restrict__ vmax, long long i,
+                          int amsgrad, const AdamScal& s) {
+#pragma clang fp contract(off)
+    const float gr = g * s.gscale;
+    const float mi = fmaf(s.w1, fmaf(s.gscale, g, -m[i]), m[i]);
+    const float vi = v[i] * s.beta2 + s.w2 * (gr * gr);
     m[i] = mi; v[i] = vi;
-    float den;
-    if (amsgrad) { const float vm = fmaxf(vmax[i], vi); vmax[i] = vm; den = sqrtf(vm) * inv_bc2s + eps; }
-    else den = sqrtf(vi) * inv_bc2s + eps;
-    p[i] = x - step_size * (mi / den);                                    // param.addcdiv_(exp_avg, denom, value=-step_size)
+    float vd = vi;
+    if (amsgrad) { vd = fmaxf(vmax[i], vi); vmax[i] = vd; }
+    const float den = fmaf(sqrtf(vd), s.inv_bc2s, s.eps);
+    return fmaf(s.decay, p, -(s.step_size * (mi / den)));
 }
 
 // ---- the optimiser step without a host round trip (round 4) -----------------------------------------------------------------------------
@@ -169,10 +180,9 @@ OARD_KERNEL __global__ void k_adamw(float* __restrict__ p, const float* __restri
 // last <= 50 gradient norms, clip if the norm exceeds it, push min(norm, max_norm) - which costs every training step a device -> host read
 // of the gradient norm BEFORE the optimiser kernel can be launched, and the device then idles while the host prepares the next step
 // (1.3 ms of a 69-ms step at B = 64).  Here the decision is one device thread: the history, the optimiser's step count and the count of
-// skipped steps live in device memory, and k_adamw_dev takes its scalars from there.
+// skipped steps live in device memory, and k_adamw<true, .> takes its scalars from there.
 // state (doubles): [0] items in the history, [1] optimiser steps taken, [2] steps skipped, [3] reserved, [4 .. 4 + cap) the history, newest
 // first (utils/training_tools.py:6-23 inserts at the front), then 8 doubles of scratch that hold the AdamScal of the current step.
-struct AdamScal { float decay, w1, beta2, w2, eps, step_size, inv_bc2s, gscale; int skip; int pad[7]; };
 
 // numpy's pairwise summation for n <= 128 (what np.mean / np.std of the 50-entry history evaluate): bit-identical to the host path
 OARD_DEV double np_sum(const double* a, int n) {
@@ -226,22 +236,6 @@ OARD_KERNEL __global__ void k_clip_decide(double* __restrict__ st, int cap, cons
     out[0] = (float)g; out[1] = (float)max_norm; out[2] = (float)gscale; out[3] = 0.f;
 }
 
-// k_adamw with the scalars of the step read from device memory; a skipped step touches nothing
-OARD_KERNEL __global__ void k_adamw_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            float* __restrict__ vmax, long long n, int amsgrad, const AdamScal* __restrict__ sc) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || sc->skip) return;
-    const float gr = g[i] * sc->gscale;
-    const float x = p[i] * sc->decay;
-    const float mi = m[i] + sc->w1 * (gr - m[i]);
-    const float vi = v[i] * sc->beta2 + sc->w2 * (gr * gr);
-    m[i] = mi; v[i] = vi;
-    float den;
-    if (amsgrad) { const float vm = fmaxf(vmax[i], vi); vmax[i] = vm; den = sqrtf(vm) * sc->inv_bc2s + sc->eps; }
-    else den = sqrtf(vi) * sc->inv_bc2s + sc->eps;
-    p[i] = x - sc->step_size * (mi / den);
-}
-
 // ---- exponential moving average of the weights (trainer/ema.py:37-47: timm's ModelEmaV2.update after every batch) ------------------------
 // ema = fl(fl(d ema) + fl(w p)), d = float32(decay), w = float32(1 - decay) (subtracted in double on the host, rounded once): two rounded
 // products and one add, which is what torch evaluates for `decay * e + (1. - decay) * m` on float32 tensors - hence no contraction here.
@@ -259,40 +253,16 @@ OARD_KERNEL __global__ void k_ema_update(float* __restrict__ ema, const float* _
     ema[i] = ema_mix(ema[i], p[i], d, w);
 }
 
-// k_adamw with the EMA line on the fresh parameter while it is still in a register: no launch, one more read and write of the bucket
-OARD_KERNEL __global__ void k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            float* __restrict__ vmax, long long n, float decay, float w1, float beta2, float w2, float eps, float step_size,
-                            float inv_bc2s, int amsgrad, float gscale, float* __restrict__ ema, float ema_d, float ema_w) {
+// The four AdamW kernels: the scalars by value (`host`, oard_adamw_step) or read from the device memory k_clip_decide wrote (DEV: `dev`,
+// oard_adamw_step_dev; a skipped step touches nothing), and with EMA the average's line on the fresh parameter while it is still in a
+// register: no launch, one more read and write of the bucket (a skipped step does not touch the average either).
+template <bool DEV, bool EMA>
+__global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                        float* __restrict__ vmax, long long n, int amsgrad, AdamScal host, const AdamScal* __restrict__ dev,
+                        float* __restrict__ ema, float ema_d, float ema_w) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float gr = g[i] * gscale;
-    const float x = p[i] * decay;
-    const float mi = m[i] + w1 * (gr - m[i]);
-    const float vi = v[i] * beta2 + w2 * (gr * gr);
-    m[i] = mi; v[i] = vi;
-    float den;
-    if (amsgrad) { const float vm = fmaxf(vmax[i], vi); vmax[i] = vm; den = sqrtf(vm) * inv_bc2s + eps; }
-    else den = sqrtf(vi) * inv_bc2s + eps;
-    const float pn = x - step_size * (mi / den);
+    if (i >= n || (DEV && dev->skip)) return;
+    const float pn = adamw_elem(p[i], g[i], m, v, vmax, i, amsgrad, DEV ? *dev : host);
     p[i] = pn;
-    ema[i] = ema_mix(ema[i], pn, ema_d, ema_w);
-}
-
-// k_adamw_dev likewise; a skipped step touches neither the weights nor their average
-OARD_KERNEL __global__ void k_adamw_dev_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                float* __restrict__ vmax, long long n, int amsgrad, const AdamScal* __restrict__ sc,
-                                float* __restrict__ ema, float ema_d, float ema_w) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || sc->skip) return;
-    const float gr = g[i] * sc->gscale;
-    const float x = p[i] * sc->decay;
-    const float mi = m[i] + sc->w1 * (gr - m[i]);
-    const float vi = v[i] * sc->beta2 + sc->w2 * (gr * gr);
-    m[i] = mi; v[i] = vi;
-    float den;
-    if (amsgrad) { const float vm = fmaxf(vmax[i], vi); vmax[i] = vm; den = sqrtf(vm) * sc->inv_bc2s + sc->eps; }
-    else den = sqrtf(vi) * sc->inv_bc2s + sc->eps;
-    const float pn = x - sc->step_size * (mi / den);
-    p[i] = pn;
-    ema[i] = ema_mix(ema[i], pn, ema_d, ema_w);
+    if (EMA) ema[i] = ema_mix(ema[i], pn, ema_d, ema_w);
 }

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import itertools
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
@@ -113,6 +114,24 @@ class DiffusionSampler:
             if e.numel():
                 e[:, :pd].addcmul_(x[:, :pd], coef)
 
+    def _denoise(self, z, t, prior_tab, at, edge_index, conditions, n_frag_switch, combined_mask):
+        """One network call at time `t` ([1] device tensor) -> eps_hat, with the prior term added when the run has a prior table: its
+        entry `at`, a slice (the eager loops: a view) or a [1] device index (the replayed loops: an index_select, issued after the
+        network call as the loops always did)."""
+        eps_hat, _ = self.dynamics(z, edge_index, t, conditions, n_frag_switch, combined_mask)
+        if prior_tab is not None:
+            self._add_prior(eps_hat, z, prior_tab[at] if isinstance(at, slice) else prior_tab.index_select(0, at))
+        return eps_hat
+
+    def _noise_source(self, noise_fn, sizes, dev):
+        """-> draw(i): the i-th set of raw N(0, 1) draws of a run, one [n_k, node_nf_k] float32 tensor per object on the device - from
+        `noise_fn(i)` (tests) if given, else torch.randn there."""
+        def draw(i):
+            if noise_fn is not None:
+                return [x.to(device=dev, dtype=torch.float32).contiguous() for x in noise_fn(i)]
+            return [torch.randn(n, nf, device=dev) for n, nf in zip(sizes, self.node_nfs)]
+        return draw
+
     # --------------------------------------------------------------------------------------------
     def _launch_step(self, topo, mode, z, eh, noise, h0, scalars, out, stream):
         """One launch of the step kernel, then the second projection for the modes that project (0 and 4).  `scalars`: the three
@@ -151,13 +170,42 @@ class DiffusionSampler:
                                            C.c_float(1.0), C.c_float(0.0), C.c_float(0.0), 1 if self.pos_only else 0, arr(out), stream)
         _capi.check(rc, "oard_sampler_step (second projection)")
 
-    def _graphed_steps(self, dyn, topo, timesteps, za, draw, h0d, edge_index, conditions, n_frag_switch, combined_mask, dev,
-                       step_callback=None):
+    def _replay(self, dev, n_steps, block, one_step, refill, step_callback=None):
+        """The capture-and-replay protocol of the graphed loops: `one_step()` run `n_steps` times on a side stream that waits for the
+        caller's - once eagerly (the warm-up torch.cuda.graph requires), then captured once and replayed - and joined back at the end.
+        `refill(first, n_rows)` draws the noise rows of steps first .. first + n_rows - 1 into the loop's tables and resets its row
+        counter; it is called before the first step and then whenever `block` steps have used a block up.  `step_callback(i)` is
+        called with the side stream current after the warm-up step and after every replay."""
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            refill(0, min(block, n_steps))
+            one_step()
+            done, in_block = 1, 1
+            if step_callback is not None:
+                step_callback(done)
+            if n_steps > 1:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=side):
+                    one_step()
+                while done < n_steps:
+                    if in_block == block:
+                        refill(done, min(block, n_steps - done))
+                        in_block = 0
+                    g.replay()
+                    done += 1
+                    in_block += 1
+                    if step_callback is not None:
+                        step_callback(done)
+        torch.cuda.current_stream(dev).wait_stream(side)
+
+    def _graphed_steps(self, topo, timesteps, za, draw, h0d, net, dev, step_callback=None):
         """The T ancestral steps of `sample` as ONE captured hipGraph replayed T times (small batches are launch-bound:
         ~100 kernel launches per step).  The per-step scalars live in device tables indexed by a device-side step counter:
         t, the three schedule coefficients and the step's noise draw; the graph holds [table lookups, oard_forward,
         oard_sampler_step_dev, its second projection (oard_sampler_step with constant scalars), z <- z_new, counter += 1].  Same
-        kernels and same arithmetic as the eager loop, so the result is bit-identical.  Captured on a side stream after an eager warm-up step, as torch.cuda.graph requires."""
+        kernels and same arithmetic as the eager loop, so the result is bit-identical.  `_replay` runs it; `net`: the network call's
+        (edge_index, conditions, n_frag_switch, combined_mask)."""
         n_obj = len(self.node_nfs)
         steps = list(reversed(range(timesteps)))
         coefs = [self.schedule.step(s, timesteps) for s in steps]
@@ -176,12 +224,10 @@ class DiffusionSampler:
         slot = torch.zeros(1, dtype=torch.long, device=dev)              # row of the current block's noise table
         z = [x.clone() for x in za]
         z_new = [torch.empty_like(x) for x in za]
-        next_call = [1]
 
-        def refill(n_rows):
+        def refill(first, n_rows):
             for r in range(n_rows):
-                d = draw(next_call[0])
-                next_call[0] += 1
+                d = draw(first + r + 1)                                  # call 0 drew the initial state
                 for k in range(n_obj):
                     noise_tab[k][r].copy_(d[k])
             slot.zero_()
@@ -190,38 +236,14 @@ class DiffusionSampler:
             t_cur = t_tab.index_select(0, counter)                       # [1]: a 1-D t = one value for every node
             coef = coef_tab.index_select(0, counter).view(3)
             noise = [nt.index_select(0, slot)[0] for nt in noise_tab]
-            eps_hat, _ = dyn(z, edge_index, t_cur, conditions, n_frag_switch, combined_mask)
-            if prior_tab is not None:
-                self._add_prior(eps_hat, z, prior_tab.index_select(0, counter))
+            eps_hat = self._denoise(z, t_cur, prior_tab, counter, *net)
             stream = torch.cuda.current_stream(dev).cuda_stream
             self._step_kernel_dev(topo, 0, z, eps_hat, noise, h0d if self.pos_only else None, coef, z_new, stream)
             for a, b in zip(z, z_new):
                 a.copy_(b)
             counter.add_(1)
             slot.add_(1)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        done = 0
-        with torch.cuda.stream(side):                                    # eager warm-up on the capture stream (step 0)
-            refill(min(block, timesteps))
-            one_step()
-            done, in_block = 1, 1
-            if step_callback is not None:
-                step_callback(done)
-            if timesteps > 1:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    one_step()
-                while done < timesteps:
-                    if in_block == block:
-                        refill(min(block, timesteps - done))
-                        in_block = 0
-                    g.replay()
-                    done += 1
-                    in_block += 1
-                    if step_callback is not None:
-                        step_callback(done)
-        torch.cuda.current_stream(dev).wait_stream(side)
+        self._replay(dev, timesteps, block, one_step, refill, step_callback)
         return z
 
     @contextlib.contextmanager
@@ -291,13 +313,9 @@ class DiffusionSampler:
         with self._run(n_samples, fragments_nodes, conditions) as (dev, layout, conditions, topo, stream):
             masks, combined_mask, edge_index, n_frag_switch = layout
             h0d = [h.to(device=dev, dtype=torch.float32).contiguous() for h in h0] if h0 is not None else None
+            net = (edge_index, conditions, n_frag_switch, combined_mask)
             sizes = [int(m.numel()) for m in masks]
-
-            def draw(i):
-                if noise_fn is not None:
-                    return [x.to(device=dev, dtype=torch.float32).contiguous() for x in noise_fn(i)]
-                return [torch.randn(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
-
+            draw = self._noise_source(noise_fn, sizes, dev)
             za = [torch.empty(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
             zb = [torch.empty_like(z) for z in za]
             self._step_kernel(topo, 2, None, None, draw(0), h0d if self.pos_only else None, 0.0, 0.0, 1.0, za, stream)
@@ -309,14 +327,11 @@ class DiffusionSampler:
                          if graph is None else bool(graph))
             if use_graph:
                 assert return_frames == 1, "intermediate frames need the eager loop"
-                za = self._graphed_steps(dyn, topo, timesteps, za, draw, h0d, edge_index, conditions, n_frag_switch,
-                                         combined_mask, dev, step_callback)
+                za = self._graphed_steps(topo, timesteps, za, draw, h0d, net, dev, step_callback)
                 call = timesteps + 1
             for s in (reversed(range(timesteps)) if not use_graph else ()):
                 co = self.schedule.step(s, timesteps)
-                eps_hat, _ = dyn(za, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
-                if ptab is not None:
-                    self._add_prior(eps_hat, za, ptab[s + 1: s + 2])
+                eps_hat = self._denoise(za, t_table[s + 1: s + 2], ptab, slice(s + 1, s + 2), *net)
                 self._step_kernel(topo, 0, za, eps_hat, draw(call), h0d if self.pos_only else None,
                                   co.alpha_ts, co.c_eps, co.sigma, zb, stream)
                 if step_callback is not None:
@@ -326,9 +341,7 @@ class DiffusionSampler:
                 if (s * return_frames) % timesteps == 0 and return_frames > 1:
                     out_samples[(s * return_frames) // timesteps] = self._unnormalize_z([z.clone() for z in za])
             fc = self.schedule.final()
-            eps_hat, _ = dyn(za, edge_index, t_table[0:1], conditions, n_frag_switch, combined_mask)
-            if ptab is not None:
-                self._add_prior(eps_hat, za, ptab[0:1])
+            eps_hat = self._denoise(za, t_table[0:1], ptab, slice(0, 1), *net)
             self._step_kernel(topo, 1, za, eps_hat, draw(call), None, fc.inv_alpha_0, fc.sigma_0, fc.sigma_x, zb, stream)
             x = zb
             self.last_x = x
@@ -345,6 +358,12 @@ class DiffusionSampler:
         data-path collective.  `gather=True` adds one host-side gather of the final samples on rank 0 (the only
         communication of the whole run).  Returns (samples, masks, (lo, hi)); with `gather` rank 0 gets the samples of the
         whole batch per object (in batch order), the other ranks their own."""
+        return self._run_sharded(self.sample, "h0", fragments_nodes, h0, conditions, seed, gather, kw)
+
+    def _run_sharded(self, run, rows_name, fragments_nodes, rows, conditions, seed, gather, kw):
+        """`sample_sharded` / `inpaint_sharded`: `run` (`sample` or `inpaint`) on this rank's reactions `shard_range(B, rank, world)` -
+        their atom counts, their conditions and, if `rows` (h0 / xh_fixed, passed on as `rows_name`) is given, object k's rows of them
+        by its cumulative atom counts -, seeded with `seed + rank`; then, if asked for, the one gather of the samples on rank 0."""
         import torch.distributed as dist
         from .shard import shard_range
         on = dist.is_available() and dist.is_initialized()
@@ -353,14 +372,14 @@ class DiffusionSampler:
         lo, hi = shard_range(B, rank, world)
         local = [f[lo:hi] for f in fragments_nodes]
         cond = conditions[lo:hi] if conditions is not None else None
-        h0l = None
-        if h0 is not None:
-            h0l = []
-            for f, h in zip(fragments_nodes, h0):
+        local_rows = None
+        if rows is not None:
+            local_rows = []
+            for f, x in zip(fragments_nodes, rows):
                 off = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.long), f.cpu().long()]), 0)
-                h0l.append(h[int(off[lo]): int(off[hi])])
+                local_rows.append(x[int(off[lo]): int(off[hi])])
         torch.manual_seed(seed + rank)                     # seeds the device generators too
-        out, masks = self.sample(hi - lo, local, conditions=cond, h0=h0l, **kw)
+        out, masks = run(hi - lo, local, conditions=cond, **{rows_name: local_rows}, **kw)
         if gather and world > 1:
             mine = (lo, [o.cpu() for o in out[0]])
             got = [None] * world if rank == 0 else None
@@ -391,11 +410,9 @@ class DiffusionSampler:
         a_j, sig_j = self.schedule.forward_jump(s, jump_to, timesteps) if jump_to is not None else (1.0, 0.0)
         return [a_s, sig_s, co.alpha_ts, co.c_eps, co.sigma, 0.0 if jump_to is None else 1.0, a_j, sig_j]
 
-    def _graphed_repaint(self, dyn, topo, timesteps, steps, fixed_mask, za, xf, draw, hsel, edge_index, conditions, n_frag_switch,
-                         combined_mask, dev):
-        """The RePaint steps of the fused `inpaint` loop as ONE captured hipGraph, replayed once per entry of `steps` - the protocol of
-        `_graphed_steps`: a side stream, one eager warm-up step, one capture, replays.  Per-step device tables indexed by a device-side
-        counter: t, the 8-float coefficient row (jump flag included: the kernel branches on it, so one launch serves both kinds of
+    def _graphed_repaint(self, topo, timesteps, steps, fixed_mask, za, xf, draw, hsel, net, dev):
+        """The RePaint steps of the fused `inpaint` loop as ONE captured hipGraph, replayed once per entry of `steps` by `_replay`, as
+        `_graphed_steps`' are.  Per-step device tables indexed by a device-side counter: t, the 8-float coefficient row (jump flag included: the kernel branches on it, so one launch serves both kinds of
         step), the prior coefficient, and three noise tables (known / step / jump) refilled in blocks of at most
         `noise_block_bytes` in the eager loop's draw order - a jump row is drawn only for the steps that jump, so a seeded run
         consumes the generator exactly like the eager loop.  The graph holds [table lookups, oard_forward, the prior axpy,
@@ -408,7 +425,8 @@ class DiffusionSampler:
         prior_tab = self._prior_table(timesteps, dev)[idx] if self.prior_std is not None else None
         per_step = 3 * 4 * sum(int(x.numel()) for x in za)
         block = max(1, min(n_steps, self.noise_block_bytes // max(per_step, 1)))
-        tabs = [[torch.empty((block,) + tuple(x.shape), dtype=torch.float32, device=dev) for x in za] for _ in range(3)]   # known, step, jump
+        # known, step, jump; zeros: a jump row is never drawn for a step that does not jump and never read, but stays finite
+        tabs = [[torch.zeros((block,) + tuple(x.shape), dtype=torch.float32, device=dev) for x in za] for _ in range(3)]
         counter = torch.zeros(1, dtype=torch.long, device=dev)           # entry of `steps` (t / coefficient / prior tables)
         slot = torch.zeros(1, dtype=torch.long, device=dev)              # row of the current block's noise tables
         z = [x.clone() for x in za]
@@ -428,36 +446,14 @@ class DiffusionSampler:
             t_cur = t_tab.index_select(0, counter)
             coef = coef_tab.index_select(0, counter).view(8)
             nk, ns, nj = ([nt.index_select(0, slot)[0] for nt in tab] for tab in tabs)
-            eps_hat, _ = dyn(z, edge_index, t_cur, conditions, n_frag_switch, combined_mask)
-            if prior_tab is not None:
-                self._add_prior(eps_hat, z, prior_tab.index_select(0, counter))
+            eps_hat = self._denoise(z, t_cur, prior_tab, counter, *net)
             stream = torch.cuda.current_stream(dev).cuda_stream
             self._inpaint_step(topo, fixed_mask, z, eps_hat, xf, nk, ns, nj, hsel, coef, z_new, stream)
             for a, b in zip(z, z_new):
                 a.copy_(b)
             counter.add_(1)
             slot.add_(1)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                                    # eager warm-up on the capture stream (entry 0)
-            for tab in tabs:                                             # rows never drawn (no jump) are never read; keep them finite
-                for nt in tab:
-                    nt.zero_()
-            refill(0, min(block, n_steps))
-            one_step()
-            done, in_block = 1, 1
-            if n_steps > 1:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    one_step()
-                while done < n_steps:
-                    if in_block == block:
-                        refill(done, min(block, n_steps - done))
-                        in_block = 0
-                    g.replay()
-                    done += 1
-                    in_block += 1
-        torch.cuda.current_stream(dev).wait_stream(side)
+        self._replay(dev, n_steps, block, one_step, refill)
         return z
 
     @torch.no_grad()
@@ -492,16 +488,11 @@ class DiffusionSampler:
             h0 = [x[:, pd:].long().to(torch.float32).contiguous() for x in xf]                 # :753
             for k in range(n_obj):                                                              # :755-759
                 xf[k][:, :pd] = EGNNDynamics.remove_mean_batch(xf[k][:, :pd], masks[k])
+            net = (edge_index, conditions, n_frag_switch, combined_mask)
             sizes = [int(m.numel()) for m in masks]
-            counter = [0]
-
-            def draw():
-                i = counter[0]
-                counter[0] += 1
-                if noise_fn is not None:
-                    return [x.to(device=dev, dtype=torch.float32).contiguous() for x in noise_fn(i)]
-                return [torch.randn(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
-
+            calls = itertools.count()                          # the draws are numbered in the order the loop asks for them
+            draw_call = self._noise_source(noise_fn, sizes, dev)
+            draw = lambda: draw_call(next(calls))              # noqa: E731
             new = lambda: [torch.empty(sizes[k], self.node_nfs[k], device=dev) for k in range(n_obj)]
             hsel = h0 if self.pos_only else None
             zt = new()
@@ -514,15 +505,12 @@ class DiffusionSampler:
             self.last_inpaint_loop = "graphed" if use_graph else "fused" if fused else "unfused"
             if use_graph:
                 assert return_frames == 1, "intermediate frames need the eager loop"
-                zt = self._graphed_repaint(dyn, topo, timesteps, steps, fixed_mask, zt, xf, draw, hsel, edge_index, conditions,
-                                           n_frag_switch, combined_mask, dev)
+                zt = self._graphed_repaint(topo, timesteps, steps, fixed_mask, zt, xf, draw, hsel, net, dev)
             elif fused:
                 spare = new()                                  # the two state lists of the whole loop, ping-ponged
                 for s, jump_to in steps:
                     nk = draw()                                                                         # :797-805
-                    eps_hat, _ = dyn(zt, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
-                    if ptab is not None:
-                        self._add_prior(eps_hat, zt, ptab[s + 1: s + 2])
+                    eps_hat = self._denoise(zt, t_table[s + 1: s + 2], ptab, slice(s + 1, s + 2), *net)
                     ns = draw()
                     nj = draw() if jump_to is not None else None                                        # :833-850
                     self._inpaint_step(topo, fixed_mask, zt, eps_hat, xf, nk, ns, nj, hsel,
@@ -537,9 +525,7 @@ class DiffusionSampler:
                     known = new()
                     self._step_kernel(topo, 3, xf, None, draw(), hsel, a_s, 0.0, sig_s, known, stream)   # :797-805
                     co = self.schedule.step(s, timesteps)
-                    eps_hat, _ = dyn(zt, edge_index, t_table[s + 1: s + 2], conditions, n_frag_switch, combined_mask)
-                    if ptab is not None:
-                        self._add_prior(eps_hat, zt, ptab[s + 1: s + 2])
+                    eps_hat = self._denoise(zt, t_table[s + 1: s + 2], ptab, slice(s + 1, s + 2), *net)
                     unknown = new()
                     self._step_kernel(topo, 0, zt, eps_hat, draw(), hsel, co.alpha_ts, co.c_eps, co.sigma, unknown, stream)
                     zt = [known[k] if k in frag_fixed else unknown[k] for k in range(n_obj)]            # :827-830
@@ -552,9 +538,7 @@ class DiffusionSampler:
                         s = t
                     s -= 1
             fc = self.schedule.final()
-            eps_hat, _ = dyn(zt, edge_index, t_table[0:1], conditions, n_frag_switch, combined_mask)
-            if ptab is not None:
-                self._add_prior(eps_hat, zt, ptab[0:1])
+            eps_hat = self._denoise(zt, t_table[0:1], ptab, slice(0, 1), *net)
             x = new()
             self._step_kernel(topo, 1, zt, eps_hat, draw(), None, fc.inv_alpha_0, fc.sigma_0, fc.sigma_x, x, stream)
             self.last_x = x
@@ -570,29 +554,7 @@ class DiffusionSampler:
         takes the reactions `shard_range(B, rank, world)` - their atom counts, conditions and the rows of every `xh_fixed[k]` (by the
         cumulative atom counts of object k) -, seeds with `seed + rank` and runs `inpaint`; no collective inside the loop.
         `gather=True`: one host-side gather of the samples on rank 0, in batch order.  Returns (samples, masks, (lo, hi))."""
-        import torch.distributed as dist
-        from .shard import shard_range
-        on = dist.is_available() and dist.is_initialized()
-        rank, world = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
-        B = int(fragments_nodes[0].numel())
-        lo, hi = shard_range(B, rank, world)
-        local = [f[lo:hi] for f in fragments_nodes]
-        cond = conditions[lo:hi] if conditions is not None else None
-        xl = []
-        for f, x in zip(fragments_nodes, xh_fixed):
-            off = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.long), f.cpu().long()]), 0)
-            xl.append(x[int(off[lo]): int(off[hi])])
-        torch.manual_seed(seed + rank)                     # seeds the device generators too
-        out, masks = self.inpaint(hi - lo, local, conditions=cond, xh_fixed=xl, **kw)
-        if gather and world > 1:
-            mine = (lo, [o.cpu() for o in out[0]])
-            got = [None] * world if rank == 0 else None
-            dist.gather_object(mine, got, dst=0)
-            if rank == 0:
-                got.sort(key=lambda t: t[0])
-                out = list(out)
-                out[0] = [torch.cat([g[1][k] for g in got], dim=0) for k in range(len(self.node_nfs))]
-        return out, masks, (lo, hi)
+        return self._run_sharded(self.inpaint, "xh_fixed", fragments_nodes, xh_fixed, conditions, seed, gather, kw)
 
     def _unnormalize_z(self, z: List[Tensor]) -> List[Tensor]:
         nv, nb, pd = self.norm_values, self.norm_biases, self.pos_dim

@@ -719,6 +719,23 @@ class DDPMTrainer:
             dyn.nan_seen.bitwise_or_(buf1.nan_seen)       # the second half's flag reaches the module's, which the step reads
         return torch.cat([nll0, nll1]), terms
 
+    def _adamw(self, entry: str, before, after) -> None:
+        """One call of the AdamW entry point `entry` - its `_ema` form when the trainer keeps an average - on the flat bucket with the
+        optimiser's hyper-parameters.  `before` / `after`: the entry point's own arguments on either side of `amsgrad`.  The weights
+        change behind torch's version counters (unless the device skipped the step: repacking is harmless)."""
+        o = self.optimizer.param_groups[0]
+        dev = self.flat_grad.device
+        args = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(), float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]),
+                float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), *before, 1 if o.get("amsgrad", False) else 0, *after)
+        if self.flat_ema is not None:
+            entry, args = entry + "_ema", args + (self.flat_ema.data_ptr(), self.ema_decay)
+        with torch.cuda.device(dev):
+            _capi.check(getattr(_capi.lib(), entry)(*args, torch.cuda.current_stream(dev).cuda_stream), entry)
+        self.dynamics.invalidate_packed()
+        if self._ema_dynamics is not None:
+            self._ema_dynamics.invalidate_packed()
+
     def _fused_step(self, batch, **kw) -> Dict[str, float]:
         dyn = self.dynamics
         prev = dyn.nan_check
@@ -745,22 +762,9 @@ class DDPMTrainer:
             stats_dev = torch.cat([norm.reshape(1), self._bucket[-1:], means])
             state = self._clip_state if self._clip_state is not None else self._push_clip_state()
             out4 = torch.empty(4, dtype=torch.float32, device=stats_dev.device)
-            o = self.optimizer.param_groups[0]
-            stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
-            args = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                    self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(), float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]),
-                    float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), 1 if o.get("amsgrad", False) else 0,
-                    1 if self.clip_grad else 0, state.data_ptr(), self.CLIP_CAPACITY, stats_dev.data_ptr(),
-                    stats_dev.data_ptr() + 4, out4.data_ptr())
-            with torch.cuda.device(self.flat_grad.device):
-                if self.flat_ema is None:
-                    _capi.check(_capi.lib().oard_adamw_step_dev(*args, stream), "oard_adamw_step_dev")
-                else:                                 # the same two launches, the average updated by the AdamW kernel (not at all if skipped)
-                    _capi.check(_capi.lib().oard_adamw_step_dev_ema(*args, self.flat_ema.data_ptr(), self.ema_decay, stream),
-                                "oard_adamw_step_dev_ema")
-            dyn.invalidate_packed()                   # the weights changed (unless the step was skipped: repacking is harmless)
-            if self._ema_dynamics is not None:
-                self._ema_dynamics.invalidate_packed()
+            # the two launches; with an average, the AdamW kernel updates it (not at all if the step is skipped)
+            self._adamw("oard_adamw_step_dev", (), (1 if self.clip_grad else 0, state.data_ptr(), self.CLIP_CAPACITY, stats_dev.data_ptr(),
+                                                    stats_dev.data_ptr() + 4, out4.data_ptr()))
             return LazyInfo(stats_dev, out4, K, [float(x) for x in self.loss.scales], self.clip_grad)
         if self._clip_state is not None:               # host_sync was switched on again: the host copies become the truth
             self._pull_clip_state()
@@ -789,21 +793,8 @@ class DDPMTrainer:
                 else:
                     self.gradnorm_queue.add(grad_norm)
                 info["grad_norm"], info["max_grad_norm"] = grad_norm, max_norm
-            o = self.optimizer.param_groups[0]
             self.opt_step += 1
-            stream = torch.cuda.current_stream(self.flat_grad.device).cuda_stream
-            args = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                    self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(), float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]),
-                    float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), self.opt_step, 1 if o.get("amsgrad", False) else 0,
-                    float(gscale))
-            with torch.cuda.device(self.flat_grad.device):
-                if self.flat_ema is None:
-                    _capi.check(_capi.lib().oard_adamw_step(*args, stream), "oard_adamw_step")
-                else:
-                    _capi.check(_capi.lib().oard_adamw_step_ema(*args, self.flat_ema.data_ptr(), self.ema_decay, stream), "oard_adamw_step_ema")
-            dyn.invalidate_packed()                   # the weights changed behind torch's version counters
-            if self._ema_dynamics is not None:
-                self._ema_dynamics.invalidate_packed()
+            self._adamw("oard_adamw_step", (self.opt_step,), (float(gscale),))
         info["loss"] = stats[2]
         info["skipped"] = int(skipped)
         return info

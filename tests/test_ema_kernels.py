@@ -1,4 +1,4 @@
-"""k_ema_update (behind oard_ema_update), k_adamw_ema (oard_adamw_step_ema) and k_adamw_dev_ema (oard_adamw_step_dev_ema) on their own.
+"""k_ema_update (behind oard_ema_update) and the EMA instantiations of k_adamw (oard_adamw_step_ema, oard_adamw_step_dev_ema) on their own.
 
 The average's semantics are pinned as `ModelEmaV2.update` in float32 (trainer/ema.py:37-47):
     ema = fl(fl(d32 * ema) + fl(w32 * p)),   d32 = float32(decay), w32 = float32(1.0 - decay)

@@ -1,4 +1,4 @@
-"""k_clip_decide / k_adamw_dev (behind oard_adamw_step_dev) and k_adamw (behind oard_adamw_step) on their own.
+"""k_clip_decide / k_adamw<DEV> (behind oard_adamw_step_dev) and k_adamw (behind oard_adamw_step) on their own.
 
 The device-side clipping decision against the host rule of DDPMTrainer (pl_trainer.py:391-418, utils/training_tools.py:6-23) restated
 here in Python floats and numpy: max_norm = 1.5 np.mean(h) + 3 np.std(h), clip if g > max_norm with the factor max_norm / (g + 1e-6),
