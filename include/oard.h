@@ -132,6 +132,27 @@ int oard_forward(const oard_config* cfg, const oard_topology* topo, const void* 
                  void* workspace_dev, size_t workspace_bytes, int32_t* status_dev,
                  oard_stream_t stream);
 
+/* ---- confidence score ---------------------------------------------------------------------------
+ * Replaces: Confidence._forward(xh, edge_index, t, conditions, n_frag_switch, combined_mask)
+ * (oa_reactdiff/dynamics/confidence.py:82-163): LEFTNet.forward with for_conf=True, which returns the node scalars s behind
+ * the last layer (model/leftnet.py:875-876), scatter_mean over the nodes of every reaction (confidence.py:157-161) and the
+ * GatedMLP readout H -> H -> H -> 1 (confidence.py:74-80, 162; model/core.py:95-131): conf = mlp(g) * sigmoid(gmlp(g)), SiLU behind
+ * layers 0 and 1 of both branches.  Inference only.
+ * Arguments as oard_forward (same packed blob - the output head's weights in it are not read -, same workspace size, same sub-batch
+ * streams, same precision bits, same poisoning), without out_dev and with
+ *   readout_dev[12]  the raw fp32 tensors readout.{mlp,gmlp}.mlp.{0,1,2}.linear.{weight,bias} in that (state-dict) order,
+ *                    weights [out][in] as nn.Linear keeps them, 16-byte aligned (rows are read four floats at a time);
+ *   conf_dev         [B] fp32: the logit of the reaction whose combined_mask value is id goes to conf_dev[id].
+ * The trunk stops behind the last layer's EquiUpdate; one launch of k_conf_readout (csrc/oard_conf.h) per sub-batch follows: fixed
+ * summation order, no atomics - a reaction's value is bit-identical run to run and does not depend on the rest of the batch.
+ * status_dev[0] is set to 1 if a written value is NaN.
+ * OARD_EINVAL: (hidden, num_radial) is not a built pair, or the reactions' combined_mask values are not exactly 0 .. B - 1 (the
+ * reference's scatter_mean would produce rows for the missing ids; its own callers never leave one out). */
+int oard_confidence_forward(const oard_config* cfg, const oard_topology* topo, const void* packed_dev,
+                            const float* const* readout_dev, const float* const* xh_dev, const float* t_dev, int t_is_scalar,
+                            const float* conditions_dev, float* conf_dev, void* workspace_dev, size_t workspace_bytes,
+                            int32_t* status_dev, oard_stream_t stream);
+
 /* Inner (same-object) edges that were inside the cutoff in the LAST inference-mode oard_forward on this workspace - the rows
  * EquiMessage actually ran (model/leftnet.py:748-753: the others carry an exactly-zero message and are skipped; equal to
  * oard_topology_num_inner_edges while nothing is masked).  A measurement aid (bench.py charges the roofline with it):

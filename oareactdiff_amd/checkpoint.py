@@ -268,3 +268,55 @@ def dynamics_from_checkpoint(ckpt: Mapping, device: torch.device = torch.device(
     )
     dyn.load_state_dict(extract_dynamics_state(ckpt["state_dict"]), strict=True)
     return dyn, hp
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The Confidence model's checkpoint: a Lightning file written from `ConfModule` (oa_reactdiff/trainer/pl_trainer.py:421-469).  Same
+# file format, same restricted unpickler; the module sits under `confidence.` and the constructor arguments are ConfModule's.
+# ---------------------------------------------------------------------------------------------------------------------
+CONFIDENCE_PREFIXES = ("confidence.", "")
+
+
+def extract_confidence_state(state_dict: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Tensors of the `Confidence` module, prefix stripped (`model.*`, `encoders.*`, `decoders.*`, `readout.*`)."""
+    for pre in CONFIDENCE_PREFIXES:
+        sub = {k[len(pre):]: v for k, v in state_dict.items()
+               if k.startswith(pre) and k[len(pre):].split(".")[0] in ("model", "encoders", "decoders", "readout")}
+        if any(k.startswith("readout.") for k in sub):
+            return sub
+    raise KeyError("no confidence tensors (confidence.model.* / .encoders.* / .decoders.* / .readout.*) found in the state dict")
+
+
+def load_confidence_checkpoint(path: str, device: torch.device = torch.device("cuda"), overrides: Optional[dict] = None):
+    """`ConfModule.load_from_checkpoint(path).confidence` for the MI355X backend: reads the file with the restricted unpickler and
+    builds `Confidence` with the checkpoint's weights (strict).  Returns (confidence, hyper_parameters)."""
+    ckpt = dict(read_checkpoint(path))
+    ckpt["hyper_parameters"] = _plain(ckpt.get("hyper_parameters", {}))
+    return confidence_from_checkpoint(ckpt, device=device, overrides=overrides)
+
+
+def confidence_from_checkpoint(ckpt: Mapping, device: torch.device = torch.device("cuda"), overrides: Optional[dict] = None):
+    """Builds `Confidence` from an already loaded `ConfModule` checkpoint dict and loads its weights with strict=True.  The
+    hyper-parameters are `ConfModule.__init__`'s (pl_trainer.py:422-440), defaults included.  Returns (confidence, hyper_parameters)."""
+    from .confidence import Confidence
+    hp = dict(ckpt.get("hyper_parameters", {}))
+    if overrides:
+        hp.update(overrides)
+    try:
+        model_config = dict(hp["model_config"])
+    except KeyError as e:
+        raise KeyError(f"checkpoint hyper_parameters lack {e}; pass them through `overrides`") from None
+    model = hp.get("model")
+    if model is not None and getattr(model, "__name__", "LEFTNet") != "LEFTNet":
+        raise NotImplementedError(f"checkpoint was trained with model={getattr(model, '__name__', model)!r}; "
+                                  "the MI355X backend implements LEFTNet only")
+    node_nfs = list(hp.get("node_nfs", [9] * 3))
+    conf = Confidence(
+        model_config=model_config,
+        fragment_names=list(hp.get("fragment_names", ["inorg_node", "org_edge", "org_node"])),
+        node_nfs=node_nfs, edge_nf=int(hp.get("edge_nf", 4)), condition_nf=int(hp.get("condition_nf", 1)),
+        pos_dim=int(hp.get("pos_dim", 3)), edge_cutoff=hp.get("edge_cutoff"), device=device,
+        enforce_same_encoding=hp.get("enforce_same_encoding"),
+    )
+    conf.load_state_dict(extract_confidence_state(ckpt["state_dict"]), strict=True)
+    return conf, hp

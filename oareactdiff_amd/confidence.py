@@ -1,0 +1,200 @@
+"""`Confidence` — drop-in for `oa_reactdiff.dynamics.confidence.Confidence(model=LEFTNet)`, the model the reference ranks generated
+transition states with (wrapped by `ConfModule`, oa_reactdiff/trainer/pl_trainer.py:421-669; production widths in
+oa_reactdiff/trainer/train_confidence_ts1x.py:42-54).
+
+It is the denoiser's LEFTNet trunk with `for_conf=True` - the node scalars behind the last layer are its output
+(model/leftnet.py:875-876) -, a mean over the nodes of every reaction and a `GatedMLP` readout H -> H -> H -> 1
+(confidence.py:74-80, 157-163).  One library call, `oard_confidence_forward` (include/oard.h): the trunk's kernels up to the last
+EquiUpdate, then `k_conf_readout` (csrc/oard_conf.h).  The module IS an `EGNNDynamics` as far as parameters, weight packing, topology
+cache and call buffers go; the twelve `readout.*` tensors are read by the kernel where they lie.
+
+INFERENCE ONLY.  There is no backward pass through the readout: the parameters are created with `requires_grad=False`, and a call with
+autograd enabled on a parameter that requires grad raises `NotImplementedError`.  Training the confidence model stays with the
+reference; its checkpoints load here (`checkpoint.load_confidence_checkpoint`)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import _capi
+from .dynamics import EGNNDynamics, _TensorKeyCache
+from .graph_tools import get_edges_index, get_mask_for_frag, get_n_frag_switch
+from .spec import READOUT_NAMES, confidence_state_spec
+
+FEATURE_MAPPING = ["pos", "one_hot", "charge"]                              # confidence.py:18
+
+
+class _Layout:
+    """Batch-layout tensors of one set of masks / sizes (what `forward` derives per call in the reference, confidence.py:170-174)."""
+
+    def __init__(self, combined_mask: Tensor, edge_index: Tensor, n_frag_switch: Tensor) -> None:
+        self.combined_mask, self.edge_index, self.n_frag_switch = combined_mask, edge_index, n_frag_switch
+        self.key_tensors = None
+
+
+def rank_candidates(scores: Tensor, n_reactions: int) -> Tuple[Tensor, Tensor]:
+    """`scores`: [K * n_reactions] scores of K candidates of each of `n_reactions` reactions, candidate-major (K repeats of the
+    batch: entry k * n_reactions + r is candidate k of reaction r) -> (best_index [n_reactions], order [n_reactions, K]): the
+    candidates of every reaction by descending score, ties by lower candidate index.  Device tensors in, device tensors out, no host
+    read."""
+    scores = scores.reshape(-1)
+    if n_reactions < 1 or scores.numel() % n_reactions:
+        raise ValueError(f"{scores.numel()} scores are not K candidates of each of {n_reactions} reactions")
+    per_reaction = scores.reshape(-1, n_reactions).t()
+    order = torch.argsort(per_reaction, dim=1, descending=True, stable=True)
+    return order[:, 0], order
+
+
+class Confidence(EGNNDynamics):
+    _for_conf = True
+
+    def __init__(
+        self,
+        model_config: Dict,
+        fragment_names: List[str],
+        node_nfs: List[int],
+        edge_nf: int,
+        condition_nf: int = 0,
+        pos_dim: int = 3,
+        edge_cutoff: Optional[float] = None,
+        model=None,
+        device: torch.device = torch.device("cuda"),
+        enforce_same_encoding: Optional[List] = None,
+        source: Optional[Dict] = None,
+        **kwargs,
+    ) -> None:
+        model_config.update({"for_conf": True})                             # confidence.py:54-56
+        super().__init__(model_config, fragment_names, node_nfs, edge_nf, condition_nf, pos_dim, True, True, edge_cutoff, model,
+                         device, enforce_same_encoding, source=source)
+        full = confidence_state_spec(model_config, node_nfs, condition_nf, pos_dim, True)
+        self._create_tensors({name: full[name] for name in READOUT_NAMES}, device)      # confidence.py:73-80
+        for p in self.parameters():                                         # inference only: nothing here can be trained
+            p.requires_grad_(False)
+        self.nan_check = "async"                                            # no host read in a call; the flag stays in `last_status`
+        self._readout_slots = None
+        self._layout_cache = _TensorKeyCache(8)                             # by the identity of the masks / sizes (forward)
+        self._size_layouts: Dict[tuple, _Layout] = {}                       # by the atom counts (score_samples), as DiffusionSampler
+        self._t0: Optional[Tensor] = None
+
+    # ------------------------------------------------------------------------------------------
+    def _readout_tensors(self, dev) -> List[Tensor]:
+        if self._readout_slots is None:
+            slots = []
+            for name in READOUT_NAMES:
+                mod = self
+                for p in name.split(".")[:-1]:
+                    mod = mod[int(p)] if p.isdigit() and isinstance(mod, torch.nn.ModuleList) else getattr(mod, p)
+                slots.append((mod, name.rsplit(".", 1)[1]))
+            self._readout_slots = slots
+        out = [mod._parameters[attr] for mod, attr in self._readout_slots]
+        for t in out:
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise _capi.OardError("the readout parameters must be contiguous float32 tensors on the call's device")
+        return out
+
+    def _forward(
+        self,
+        xh: List[Tensor],
+        edge_index: Tensor,
+        t: Tensor,
+        conditions: Tensor,
+        n_frag_switch: Tensor,
+        combined_mask: Tensor,
+        edge_attr: Optional[Tensor] = None,
+    ) -> Tensor:
+        """confidence.py:82-163 -> [B] float32 logits, squeezed like the reference's (0-d for B = 1).  Row b belongs to the reaction
+        whose `combined_mask` value is b."""
+        if edge_attr is not None:
+            raise NotImplementedError("edge attributes are not part of the LEFTNet path")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("the MI355X Confidence model is inference only: a parameter requires grad and autograd is enabled, but "
+                                      "there is no backward pass through the readout (call under torch.no_grad(), or train the confidence "
+                                      "model with the reference and load its checkpoint)")
+        dev = xh[0].device
+        if dev.type != "cuda":
+            raise _capi.OardError("Confidence needs tensors on a ROCm device (no CPU fallback)")
+        L = _capi.lib()
+        cfg = self._config()
+        if L.oard_supported(C.byref(cfg)) != _capi.OARD_OK:
+            raise NotImplementedError(f"hidden_channels={int(cfg.hidden)}, num_radial={int(cfg.num_radial)} is not a width pair the production "
+                                      "kernels were built for, and the confidence readout runs behind those only - rebuild: "
+                                      f"OARD_DIMS=\"196x96,{int(cfg.hidden)}x{int(cfg.num_radial)}\" python -m oareactdiff_amd.build")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            packed = self._get_packed(cfg, stream)
+            topo = self._get_topology(cfg, edge_index, n_frag_switch, combined_mask, stream)
+            if topo.handle is None:
+                raise NotImplementedError("edge_index is not the complete graph per reaction (get_edges_index(combined_mask, "
+                                          "remove_self_edge=True)): the confidence model runs on the production kernels only, not on the "
+                                          "general-edge-list path")
+            if topo.max_sample_id != topo.n_samples - 1:
+                raise _capi.OardError(f"combined_mask must name the reactions 0 .. B-1 with none missing: {topo.n_samples} reactions, "
+                                      f"largest id {topo.max_sample_id}")
+            xs, tt, t_scalar, cond = self._inputs(topo, xh, t, conditions, dev)
+            conf = torch.empty(topo.n_samples, dtype=torch.float32, device=dev)
+            buffers = self._call_buffers
+            ws = buffers.workspace(L.oard_workspace_bytes(C.byref(cfg), topo.handle), dev)
+            status = torch.zeros(2, dtype=torch.int32, device=dev)
+            rc = L.oard_confidence_forward(C.byref(cfg), topo.handle, packed.data_ptr(), _capi.ptr_array(self._readout_tensors(dev)),
+                                           _capi.ptr_array(xs), tt.data_ptr(), t_scalar, cond.data_ptr() if cond is not None else None,
+                                           conf.data_ptr(), ws.data_ptr(), ws.numel(), status.data_ptr(), stream)
+            _capi.check(rc, "oard_confidence_forward")
+            self._last_topo = topo
+            self.last_status = status
+            buffers.note(status)
+        return conf.squeeze()
+
+    def _zero_time(self, dev) -> Tensor:
+        if self._t0 is None or self._t0.device != dev:
+            self._t0 = torch.zeros(1, dtype=torch.float32, device=dev)       # confidence.py:187: t = torch.tensor([0])
+        return self._t0
+
+    def forward(self, representations: List[Dict], conditions: Tensor) -> Tensor:
+        """confidence.py:165-193.  The layout tensors are cached by the identity of the representations' masks and sizes: a caller that
+        scores batch after batch of one layout pays for the edge list and the index tables once."""
+        masks = [r["mask"] for r in representations]
+        sizes = [r["size"] for r in representations]
+
+        dev = representations[0]["pos"].device
+
+        def build():
+            combined_mask = torch.cat(masks).to(dev)
+            return _Layout(combined_mask, get_edges_index(combined_mask, remove_self_edge=True),
+                           get_n_frag_switch([s.to(dev) for s in sizes]))
+        lay = self._layout_cache.lookup(tuple(masks) + tuple(sizes), (str(dev),), build)
+        xh = [torch.cat([r[f] for f in FEATURE_MAPPING], dim=1) for r in representations]
+        return self._forward(xh=xh, edge_index=lay.edge_index, t=self._zero_time(dev), conditions=conditions,
+                             n_frag_switch=lay.n_frag_switch, combined_mask=lay.combined_mask, edge_attr=None)
+
+    # ------------------------------------------------------------------------------------------
+    def _layout_of_sizes(self, fragments_nodes: List[Tensor], dev) -> _Layout:
+        key = tuple(tuple(int(v) for v in f.tolist()) for f in fragments_nodes)
+        hit = self._size_layouts.get(key)
+        if hit is None or hit.combined_mask.device != dev:
+            fn = [f.to(dev) for f in fragments_nodes]
+            combined_mask = torch.cat([get_mask_for_frag(f) for f in fn])
+            hit = _Layout(combined_mask, get_edges_index(combined_mask, remove_self_edge=True), get_n_frag_switch(fn))
+            if len(self._size_layouts) >= 4:
+                self._size_layouts.pop(next(iter(self._size_layouts)))
+            self._size_layouts[key] = hit
+        return hit
+
+    @torch.no_grad()
+    def score_samples(self, fragments_nodes: List[Tensor], samples: List[Tensor], conditions: Optional[Tensor] = None,
+                      probability: bool = True) -> Tensor:
+        """Scores what `DiffusionSampler.sample` / `inpaint` return: `samples` = `out_samples[0]`, one [n_k, node_nf_k] tensor
+        [pos | one_hot | charge] per object, laid out by `fragments_nodes` (atoms per reaction, per object).  -> [B] scores;
+        `probability`: the sigmoid of the logits, as `ConfModule` applies it (pl_trainer.py:565).  The samples stay on the device."""
+        dev = next(self.parameters()).device
+        lay = self._layout_of_sizes(fragments_nodes, dev)
+        if conditions is None:
+            conditions = torch.zeros(int(fragments_nodes[0].numel()), max(self.condition_nf, 1), device=dev)
+        xh = [x.to(device=dev, dtype=torch.float32) for x in samples]
+        logits = self._forward(xh, lay.edge_index, self._zero_time(dev), conditions.to(dev), lay.n_frag_switch, lay.combined_mask)
+        logits = logits.reshape(-1)
+        return torch.sigmoid(logits) if probability else logits
+
+    rank_candidates = staticmethod(rank_candidates)

@@ -24,10 +24,11 @@
 #include "oard_edge_bwd.h"
 #include "oard_node_bwd.h"
 #include "oard_rows.h"
+#include "oard_conf.h"       // k_conf_readout: the Confidence model's pooled gated readout (oard_confidence_forward)
 #include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
-#define OARD_VERSION 2042      // + oard_kabsch_rmsd (2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
+#define OARD_VERSION 2043      // + oard_confidence_forward (2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
 // The first-generation kernels (weights straight from L2, one wave per 16 nodes: gcl_variant / equi_variant / node_variant 0) are the
 // A/B baseline of round 1 and a cross-check in tests/test_hip_parity.py::test_every_kernel_variant_is_parity_green; they are compiled
 // into experiment builds (-DOARD_EXPERIMENTS) only - a product library refuses those variants (oard_debug_option returns OARD_EINVAL).
@@ -537,10 +538,13 @@ static TapeOff make_tape(const oard_config* c, const TopoDev& td) {
 // buffer (the update is out of place), the edge kernels store their pre-activations, and the node state at the
 // layer boundaries is written straight into its tape slots (no copies).  Every launch shape comes from the plan (oard_plan.h), made here
 // once from the caller's copy of the options.
+// `conf` != NULL (oard_confidence_forward, inference only): the trunk stops behind the last layer's EquiUpdate - no output head, `out`
+// is not used - and the readout kernel (oard_conf.h) turns the final node scalars into one value per reaction, conf->out[id].
+struct ConfHead { ConfReadout w; float* out; };
 template <class D>
 static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoPart* topo, const float* wb, const float* const* xh,
                         const float* t, int t_scalar, const float* cond, float* const* out, char* ws, char* tape,
-                        int* status, hipStream_t st) {
+                        int* status, hipStream_t st, const ConfHead* conf = nullptr) {
     const TopoDev& tp = topo->d;
     const PackOff po = make_layout(c);
     const WsOff w = make_ws(c, tp);
@@ -570,7 +574,7 @@ static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoP
     ObjPtrs op;
     memset(&op, 0, sizeof(op));
     for (int k = 0; k < c->n_obj; ++k) {
-        op.xh[k] = xh[k]; op.out[k] = out[k]; op.node_nf[k] = c->node_nf[k]; op.enc[k] = po.enc[k]; op.dec[k] = po.dec[k];
+        op.xh[k] = xh[k]; op.out[k] = out ? out[k] : nullptr; op.node_nf[k] = c->node_nf[k]; op.enc[k] = po.enc[k]; op.dec[k] = po.dec[k];
     }
     const long long N = tp.N, E = tp.E, A = tp.A;
     const unsigned gN = (unsigned)cdiv(N, 64), gA = (unsigned)cdiv(A, 64);
@@ -710,6 +714,14 @@ static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoP
         }
         add(to.geo, (size_t)A, GEO_STRIDE); add(to.rbuf, (size_t)A, D::RP);
         if (z.count > 0) LAUNCH(F_OTHER, k_zero_rows, z.count, 256, st, z);
+    }
+    if (conf) {
+        if (train) return OARD_EINVAL;
+        ScopedLaunch sl_(F_OTHER, st);
+        hipLaunchKernelGGL(k_conf_readout, dim3((unsigned)tp.B), dim3(CONF_WAVES * 64), 5 * D::H * sizeof(double), st, tp,
+                           (const float*)s_at(c->num_layers), D::H, D::HP, conf->w, conf->out, status);
+        HIP_TRY(hipGetLastError());
+        return OARD_OK;
     }
     if (plan.init_v1)
         LAUNCH(F_NODE, (k_out_v1<D, NW>), gNb, NW * 64, st, tp, wb, po, (const float*)s_at(c->num_layers), (const float*)vcur, dpos, hout, status);
@@ -1374,6 +1386,7 @@ int oard_topology_create_parts(const oard_config* c, const int64_t* cm, const in
     oard_topology* tp = new oard_topology();
     (void)hipGetDevice(&tp->device);
     tp->n_obj = n_obj; tp->B = B; tp->n_parts = n_parts;
+    tp->ids_dense = samples.front() == 0 && samples.back() == B - 1;       // B distinct values inside [0, B - 1]: all of them
     {   // reference-order tables of oard_topology_check_edge_index: sample, rank inside the sample, first edge id of every node
         std::vector<int> tab(2 * (size_t)N), seen(B, 0);
         for (int r = 0; r < N; ++r) { tab[r] = dense[r]; tab[(size_t)N + r] = seen[dense[r]]++; }
@@ -1517,11 +1530,12 @@ int oard_active_inner_edges(const oard_config* c, const oard_topology* topo, con
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-int oard_forward(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* xh,
-                 const float* t, int t_is_scalar, const float* cond, float* const* out, void* ws, size_t ws_bytes,
-                 int32_t* status, oard_stream_t stream) {
+// the inference call of oard_forward (`conf` NULL) and oard_confidence_forward: validation, poisoning and the sub-batch fork / join
+static int forward_parts(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* xh,
+                         const float* t, int t_is_scalar, const float* cond, float* const* out, void* ws, size_t ws_bytes,
+                         int32_t* status, oard_stream_t stream, const ConfHead* conf) {
     topo_touch(topo, (hipStream_t)stream);
-    if (!config_ok(c) || !topo || !packed || !xh || !out || !ws || !status) return OARD_EINVAL;
+    if (!config_ok(c) || !topo || !packed || !xh || (!out && !conf) || !ws || !status) return OARD_EINVAL;
     if (c->condition_time && !t) return OARD_EINVAL;
     if (c->condition_nf > 0 && !cond) return OARD_EINVAL;
     if (c->n_obj != topo->n_obj) return OARD_EINVAL;
@@ -1538,13 +1552,36 @@ int oard_forward(const oard_config* c, const oard_topology* topo, const void* pa
         if (concurrent && p > 0) HIP_TRY(hipStreamWaitEvent(sp, topo->ev_fork, 0));
         int rc = OARD_EINVAL;
         DISPATCH_DIMS(c, rc = forward_impl<D>(opt, c, &topo->parts[p], (const float*)packed, xh, t, t_is_scalar, cond, out,
-                                              (char*)ws + topo->parts[p].ws_off, nullptr, (int*)status, sp));
+                                              (char*)ws + topo->parts[p].ws_off, nullptr, (int*)status, sp, conf));
         if (rc != OARD_OK) return rc;
         if (concurrent && p > 0) HIP_TRY(hipEventRecord(topo->ev_join[p], sp));
     }
     if (concurrent)
         for (int p = 1; p < topo->n_parts; ++p) HIP_TRY(hipStreamWaitEvent(st, topo->ev_join[p], 0));
     return OARD_OK;
+}
+
+int oard_forward(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* xh,
+                 const float* t, int t_is_scalar, const float* cond, float* const* out, void* ws, size_t ws_bytes,
+                 int32_t* status, oard_stream_t stream) {
+    if (!out) return OARD_EINVAL;
+    return forward_parts(c, topo, packed, xh, t, t_is_scalar, cond, out, ws, ws_bytes, status, stream, nullptr);
+}
+
+// Confidence._forward (oa_reactdiff/dynamics/confidence.py:82-163): the trunk up to the last layer's node scalars, then k_conf_readout
+// once per sub-batch on that sub-batch's stream.  conf_dev is indexed by the reactions' combined_mask values, so those must be
+// 0 .. B - 1 with none missing (what scatter_mean's output rows are in the reference).
+int oard_confidence_forward(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* readout,
+                            const float* const* xh, const float* t, int t_is_scalar, const float* cond, float* conf_out,
+                            void* ws, size_t ws_bytes, int32_t* status, oard_stream_t stream) {
+    if (!config_ok(c) || !topo || !readout || !conf_out || !topo->ids_dense) return OARD_EINVAL;
+    ConfHead head;
+    for (int i = 0; i < 12; ++i) {          // (the kernel reads the weight rows as float4)
+        if (!readout[i] || (i % 2 == 0 && ((uintptr_t)readout[i] & 15))) return OARD_EINVAL;
+        head.w.p[i] = readout[i];
+    }
+    head.out = conf_out;
+    return forward_parts(c, topo, packed, xh, t, t_is_scalar, cond, nullptr, ws, ws_bytes, status, stream, &head);
 }
 
 static int sampler_step_impl(const oard_config* c, const oard_topology* topo, int mode, const float* const* z,

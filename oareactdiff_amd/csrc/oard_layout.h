@@ -131,6 +131,7 @@ struct oard_topology {
     int n_parts = 0;
     TopoPart parts[OARD_MAX_PARTS];
     int n_obj = 0, B = 0;
+    bool ids_dense = false;        // the samples' combined_mask values are exactly 0 .. B - 1 (oard_confidence_forward writes row id)
     long long N = 0, E = 0, A = 0;
     int max_group = 0, max_ns = 0;
     int obj_start[OARD_MAX_OBJECTS + 1] = {};   // reference (object-major) row ranges of the objects

@@ -102,6 +102,9 @@ class _TensorKeyCache(OrderedDict):
 
 
 class EGNNDynamics(nn.Module):
+    #: model_config["for_conf"] this class runs: the denoiser's output head here, the pooled readout in `confidence.Confidence`
+    _for_conf = False
+
     def __init__(
         self,
         model_config: Dict,
@@ -131,7 +134,7 @@ class EGNNDynamics(nn.Module):
         if model_config["act_fn"] not in ("swish", "silu"):
             raise NotImplementedError("only the swish/silu activation is implemented")
         for key, want in (("legacy", True), ("update", True), ("pos_grad", False), ("single_layer_output", True),
-                          ("object_aware", True), ("for_conf", False), ("ff", False)):       # reflect_equiv: both settings
+                          ("object_aware", True), ("for_conf", self._for_conf), ("ff", False)):       # reflect_equiv: both settings
             if model_config.get(key, want) != want:
                 raise NotImplementedError(f"model_config[{key!r}] must be {want} for the MI355X backend")
         if "in_edge_nf" in model_config:
@@ -168,36 +171,7 @@ class EGNNDynamics(nn.Module):
         self.model = _Node()
         self.encoders = nn.ModuleList([_Node() for _ in node_nfs])
         self.decoders = nn.ModuleList([_Node() for _ in node_nfs])
-        means, betas = rbf_buffers(R, float(model_config.get("cutoff", 10.0)))
-        for name, (shape, kind, fan_in) in self._spec.items():
-            parts = name.split(".")
-            mod: nn.Module = self
-            for p in parts[:-1]:
-                if p.isdigit() and isinstance(mod, nn.ModuleList):
-                    mod = mod[int(p)]
-                else:
-                    if not hasattr(mod, p):
-                        mod.add_module(p, _Node())
-                    mod = getattr(mod, p)
-            leaf = parts[-1]
-            if kind == "buf_means":
-                mod.register_buffer(leaf, means.clone().to(device))
-            elif kind == "buf_betas":
-                mod.register_buffer(leaf, betas.clone().to(device))
-            else:
-                t = torch.empty(shape, dtype=torch.float32, device=device)
-                if kind == "ln_w":
-                    nn.init.ones_(t)
-                elif kind == "ln_b":
-                    nn.init.zeros_(t)
-                elif kind == "w" and _xavier_names(name):
-                    nn.init.xavier_uniform_(t)
-                elif kind == "b" and ".update_net." in name:
-                    nn.init.zeros_(t)
-                else:
-                    bound = 1.0 / math.sqrt(fan_in)                      # nn.Linear default scale
-                    nn.init.uniform_(t, -bound, bound)
-                mod.register_parameter(leaf, nn.Parameter(t))
+        self._create_tensors(self._spec, device)
         if enforce_same_encoding is not None:                             # _base.py:110-113
             for ii in enforce_same_encoding:
                 self.encoders[ii] = self.encoders[0]
@@ -235,6 +209,39 @@ class EGNNDynamics(nn.Module):
         #: "general": every inference call runs the general path (tests: two independent implementations of the same network)
         self.edge_list_path = "auto"
         self._warned_unbuilt = False
+
+    def _create_tensors(self, spec, device) -> None:
+        """Registers the parameters and buffers `spec` names, under the reference's module tree, with the reference's initial values."""
+        means, betas = rbf_buffers(self._dims[1], float(self.model_config.get("cutoff", 10.0)))
+        for name, (shape, kind, fan_in) in spec.items():
+            parts = name.split(".")
+            mod: nn.Module = self
+            for p in parts[:-1]:
+                if p.isdigit() and isinstance(mod, nn.ModuleList):
+                    mod = mod[int(p)]
+                else:
+                    if not hasattr(mod, p):
+                        mod.add_module(p, _Node())
+                    mod = getattr(mod, p)
+            leaf = parts[-1]
+            if kind == "buf_means":
+                mod.register_buffer(leaf, means.clone().to(device))
+            elif kind == "buf_betas":
+                mod.register_buffer(leaf, betas.clone().to(device))
+            else:
+                t = torch.empty(shape, dtype=torch.float32, device=device)
+                if kind == "ln_w":
+                    nn.init.ones_(t)
+                elif kind == "ln_b":
+                    nn.init.zeros_(t)
+                elif kind == "w" and _xavier_names(name):
+                    nn.init.xavier_uniform_(t)
+                elif kind == "b" and ".update_net." in name:
+                    nn.init.zeros_(t)
+                else:
+                    bound = 1.0 / math.sqrt(fan_in)                      # nn.Linear default scale
+                    nn.init.uniform_(t, -bound, bound)
+                mod.register_parameter(leaf, nn.Parameter(t))
 
     @property
     def _ws(self) -> Optional[Tensor]:

@@ -105,6 +105,24 @@ def state_spec(model_config: Dict, node_nfs: List[int], condition_nf: int, pos_d
     return spec
 
 
+#: the Confidence model's GatedMLP readout (oa_reactdiff/dynamics/confidence.py:74-80, model/core.py:95-131), in state-dict order
+READOUT_NAMES = tuple(f"readout.{branch}.mlp.{layer}.linear.{leaf}"
+                      for branch in ("mlp", "gmlp") for layer in range(3) for leaf in ("weight", "bias"))
+
+
+def confidence_state_spec(model_config: Dict, node_nfs: List[int], condition_nf: int, pos_dim: int = 3,
+                          condition_time: bool = True) -> "OrderedDict[str, SpecEntry]":
+    """State-dict layout of the reference's `Confidence(model=LEFTNet)`: `state_spec` (the decoders are still there, unused) plus
+    the twelve tensors of `readout`, two H -> H -> H -> 1 stacks."""
+    spec = state_spec(model_config, node_nfs, condition_nf, pos_dim, condition_time)
+    H = model_dims(model_config)[0]
+    for name in READOUT_NAMES:
+        layer = int(name.split(".")[3])
+        out = 1 if layer == 2 else H
+        spec[name] = ((out, H), "w", H) if name.endswith("weight") else ((out,), "b", H)
+    return spec
+
+
 # ---- integer-hash uniform generator ----------------------------------------------------------
 _MASK = np.uint64(0xFFFFFFFFFFFFFFFF)
 
