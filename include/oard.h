@@ -137,7 +137,7 @@ int oard_forward(const oard_config* cfg, const oard_topology* topo, const void* 
  * (oa_reactdiff/dynamics/confidence.py:82-163): LEFTNet.forward with for_conf=True, which returns the node scalars s behind
  * the last layer (model/leftnet.py:875-876), scatter_mean over the nodes of every reaction (confidence.py:157-161) and the
  * GatedMLP readout H -> H -> H -> 1 (confidence.py:74-80, 162; model/core.py:95-131): conf = mlp(g) * sigmoid(gmlp(g)), SiLU behind
- * layers 0 and 1 of both branches.  Inference only.
+ * layers 0 and 1 of both branches.  Inference; the training-mode call and its backward: "training the confidence model" below.
  * Arguments as oard_forward (same packed blob - the output head's weights in it are not read -, same workspace size, same sub-batch
  * streams, same precision bits, same poisoning), without out_dev and with
  *   readout_dev[12]  the raw fp32 tensors readout.{mlp,gmlp}.mlp.{0,1,2}.linear.{weight,bias} in that (state-dict) order,
@@ -446,6 +446,39 @@ int oard_train_stage_backward(const oard_config* cfg, const oard_topology* topo,
  * mean; otherwise nothing is written.  Asynchronous on `stream`. */
 int oard_nan_replace(const oard_config* cfg, const oard_topology* topo, const int32_t* status_dev, const float* const* noise_dev,
                      float* const* out_dev, oard_stream_t stream);
+
+/* ---- training the confidence model ---------------------------------------------------------------------------------------------
+ * Replaces: torch autograd through Confidence._forward (oa_reactdiff/dynamics/confidence.py:82-163) when ConfModule.training_step
+ * (oa_reactdiff/trainer/pl_trainer.py:554-617) back-propagates its BCE / MSE loss.  The reference has no hand-written backward.
+ *
+ * oard_confidence_forward_train: oard_forward_train's arguments without out_dev, plus readout_dev[12] and conf_dev [B] as in
+ * oard_confidence_forward.  The training-mode trunk with the tape written (cfg.precision handed through unchanged) stops behind the last
+ * layer's EquiUpdate; k_conf_readout then runs on the tape's S_IN[L].  OARD_EINVAL as for oard_confidence_forward (unbuilt width pair,
+ * reaction ids not exactly 0 .. B - 1, a missing or misaligned readout tensor) and, like oard_forward_train, for a topology of more
+ * than one sub-batch.
+ *
+ * oard_confidence_tail_backward: the confidence counterpart of oard_train_tail_backward, the first call of a sweep; then
+ * oard_train_layer_backward for l = L-1 .. 0 and oard_train_init_backward as for the denoiser (they take the final edge state's
+ * cotangent as zero; the last layer's vec-side adjoints run on dvec = 0).
+ *   in : tape_dev           the tape of oard_confidence_forward_train
+ *        readout_dev[12]    as above
+ *        dconf_dev [B]      fp32, d loss / d logit, indexed by the reaction's combined_mask value like conf_dev
+ *   out: ds_dev [N][HP]     cotangent of the final node scalars: dg / n_b in the columns < H of every node of reaction b, exact zeros
+ *                           in the pad columns (the buffer may arrive uninitialised)
+ *        dvec_dev [3N][HP]  exact zeros (nothing flows into vec under for_conf)
+ *        readout_grads_dev[12]  nn.Linear shapes in readout_dev's order; NULL entries are skipped; ACCUMULATED into, like grads_dev
+ * Two launches on `stream` (csrc/oard_conf_bwd.h): k_conf_readout_bwd, one workgroup per reaction, recomputes the readout in float64
+ * from the taped s (no extra tape entry, pad columns of s never read) and leaves the weight gradients' operands in the scratch;
+ * k_conf_wgrad sums them over the reactions in ascending order in float64 and adds once, in float32, into the destination.  No atomics:
+ * bit-identical run to run.  scratch_dev: the sweep's scratch (oard_train_scratch_bytes covers the 72 H + 16 bytes per reaction this
+ * call uses; OARD_ENOMEM otherwise), poisoned first under the "poison" debug option.  Nothing synchronises. */
+int oard_confidence_forward_train(const oard_config* cfg, const oard_topology* topo, const void* packed_dev,
+                                  const float* const* readout_dev, const float* const* xh_dev, const float* t_dev, int t_is_scalar,
+                                  const float* conditions_dev, float* conf_dev, void* workspace_dev, size_t workspace_bytes,
+                                  void* tape_dev, size_t tape_bytes, int32_t* status_dev, oard_stream_t stream);
+int oard_confidence_tail_backward(const oard_config* cfg, const oard_topology* topo, const void* tape_dev,
+                                  const float* const* readout_dev, const float* dconf_dev, float* ds_dev, float* dvec_dev,
+                                  float* const* readout_grads_dev, void* scratch_dev, size_t scratch_bytes, oard_stream_t stream);
 
 /* ---- The training caller around the network call, fused (round 3) --------------------------------------------------------------
  * oard_loss_prepare  EnVariationalDiffusion.forward up to the network call (en_diffusion.py:56-123, noised_representation :250-281,

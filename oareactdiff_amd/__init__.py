@@ -1,7 +1,8 @@
 """oareactdiff_amd — MI355X (gfx950) backend for OA-ReactDiff's per-timestep denoising call.
 
     from oareactdiff_amd import EGNNDynamics        # drop-in for oa_reactdiff.dynamics.EGNNDynamics(model=LEFTNet)
-    from oareactdiff_amd import Confidence          # drop-in for oa_reactdiff.dynamics.confidence.Confidence(model=LEFTNet), inference
+    from oareactdiff_amd import Confidence          # drop-in for oa_reactdiff.dynamics.confidence.Confidence(model=LEFTNet)
+    from oareactdiff_amd import ConfidenceTrainer   # ConfModule's training step for Confidence(..., trainable=True)
 
 See DESIGN.md (path, kernels, measurement) and INTEGRATION.md (binding)."""
 from .dynamics import EGNNDynamics  # noqa: F401
@@ -9,6 +10,7 @@ from .confidence import Confidence, rank_candidates  # noqa: F401
 from .sampler import DiffusionSampler  # noqa: F401
 from .loss import DiffusionLoss  # noqa: F401
 from .trainer import DDPMTrainer  # noqa: F401
+from .conf_trainer import ConfidenceTrainer  # noqa: F401
 from .graph_tools import get_edges_index, get_mask_for_frag, get_n_frag_switch, get_subgraph_mask  # noqa: F401
 
-__all__ = ["EGNNDynamics", "Confidence", "rank_candidates", "DiffusionSampler", "DiffusionLoss", "DDPMTrainer", "get_edges_index", "get_mask_for_frag", "get_n_frag_switch", "get_subgraph_mask"]
+__all__ = ["EGNNDynamics", "Confidence", "rank_candidates", "DiffusionSampler", "DiffusionLoss", "DDPMTrainer", "ConfidenceTrainer", "get_edges_index", "get_mask_for_frag", "get_n_frag_switch", "get_subgraph_mask"]

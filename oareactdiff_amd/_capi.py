@@ -8,7 +8,7 @@ import os
 from .build import LIB
 
 OARD_MAX_OBJECTS = 8
-ABI_VERSION = 2043            # OARD_VERSION of csrc/oard_hip.hip (checked by lib(): a stale library is refused, not misread)
+ABI_VERSION = 2044            # OARD_VERSION of csrc/oard_hip.hip (checked by lib(): a stale library is refused, not misread)
 OARD_OK, OARD_EINVAL, OARD_ENOTCOMPLETE, OARD_EHIP, OARD_ENOMEM = 0, -1, -2, -3, -4
 ERRORS = {OARD_EINVAL: "invalid argument / unsupported configuration", OARD_ENOTCOMPLETE: "topology is not complete-per-sample",
           OARD_EHIP: "HIP runtime error", OARD_ENOMEM: "workspace too small"}
@@ -30,7 +30,7 @@ EXPORTS = ["oard_version", "oard_supported", "oard_param_count", "oard_packed_by
            "oard_adamw_step_ema", "oard_adamw_step_dev_ema", "oard_ema_update", "oard_kabsch_rmsd",
            "oard_graph_create", "oard_graph_destroy", "oard_graph_num_nodes", "oard_graph_num_edges", "oard_graph_object_rows",
            "oard_graph_is_complete", "oard_graph_workspace_bytes", "oard_graph_forward", "oard_library_stream",
-           "oard_confidence_forward"]
+           "oard_confidence_forward", "oard_confidence_forward_train", "oard_confidence_tail_backward"]
 STAGE_RECOMPUTE, STAGE_UPDATE, STAGE_MESSAGE, STAGE_GCL_NODE, STAGE_NODE_PRE, STAGE_GCL_EDGE, STAGE_EQUI_EDGE = range(7)
 SCRATCH_XH, SCRATCH_XQ, SCRATCH_CR, SCRATCH_DCD, SCRATCH_DCR = range(1, 6)
 
@@ -103,6 +103,10 @@ def lib() -> C.CDLL:
     L.oard_forward.restype = C.c_int
     L.oard_confidence_forward.argtypes = [cfgp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, C.c_int, vp, vp, vp, sz, vp, vp]
     L.oard_confidence_forward.restype = C.c_int
+    L.oard_confidence_forward_train.argtypes = [cfgp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, C.c_int, vp, vp, vp, sz, vp, sz, vp, vp]
+    L.oard_confidence_forward_train.restype = C.c_int
+    L.oard_confidence_tail_backward.argtypes = [cfgp, vp, vp, C.POINTER(vp), vp, vp, vp, C.POINTER(vp), vp, sz, vp]
+    L.oard_confidence_tail_backward.restype = C.c_int
     L.oard_debug_lin3u_table.argtypes = [cfgp, vp, C.c_int, vp, vp]; L.oard_debug_lin3u_table.restype = C.c_int
     L.oard_active_inner_edges.argtypes = [cfgp, vp, vp, sz, C.POINTER(i64), vp]; L.oard_active_inner_edges.restype = C.c_int
     L.oard_sampler_step.argtypes = [cfgp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),

@@ -1,0 +1,235 @@
+"""One training step of the confidence model around the HIP `Confidence` module.
+
+`ConfidenceTrainer.training_step` mirrors `ConfModule.training_step` + `compute_loss` + `configure_optimizers` +
+`configure_gradient_clipping` (oa_reactdiff/trainer/pl_trainer.py:421-669, driven by trainer/train_confidence_ts1x.py):
+
+    preds = confidence.forward(representations, conditions)          pl_trainer.py:559-562
+    loss  = BCELoss(sigmoid(preds), target.float())                  :564-565, 584   (classification)
+          | MSELoss(preds, target.float())                           :584            (regression)
+    loss.backward()                                                  HIP: oard_confidence_tail_backward + the denoiser's sweep
+    adaptive gradient clipping, 2.5 mean + 3 std of the norm history :642-669        (the denoiser's trainer uses 1.5)
+    AdamW step                                                       :488-499
+
+The step builds no autograd graph: the training-mode forward (`oard_confidence_forward_train`), the closed-form cotangent of the loss,
+(sigmoid(x) - y) / B or 2 (x - y) / B - a few element-wise torch ops on [B] -, the reverse sweep straight into ONE flat gradient bucket and
+`oard_adamw_step` on ONE flat parameter buffer, as in `DDPMTrainer`'s fused step.  One host read per step: [gradient norm, non-finite
+flag, loss, logged metrics].
+
+Logged (`info`): classification `acc`, `precision`, `F1` at threshold 0.5 and `mean` (the share of predictions that round to 1);
+regression `MAE` and `mean` - torch ops on the device.  The reference also logs `AUC` (classification), `Pearson` and `Spearman`
+(regression) through torchmetrics, which this package does not depend on: they are left out.
+
+Host-sync step on one device only: no `host_sync=False`, no micro-batches, no process group (out of scope).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, List, Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import _capi
+from .confidence import FEATURE_MAPPING, Confidence, _Layout
+from .graph_tools import get_n_frag_switch
+from .trainer import Queue
+
+DEFAULT_OPTIMIZER = dict(lr=5e-4, betas=(0.9, 0.999), weight_decay=0, amsgrad=True)       # train_confidence_ts1x.py:82-87
+CLIP_MEAN_FACTOR, CLIP_STD_FACTOR = 2.5, 3.0                                                # pl_trainer.py:649
+
+
+class ConfidenceTrainer:
+    def __init__(self, confidence: Confidence, optimizer_config: Optional[Dict] = None, clip_grad: bool = True,
+                 classification: bool = True, target_key: str = "rmsd", ema_decay: Optional[float] = None):
+        """`confidence`: a `Confidence(..., trainable=True)` on a ROCm device.  A batch is `(representations, res)` with
+        `res["condition"]` and the targets `res[target_key]` ([B], by reaction id), as `ConfModule.compute_loss` takes it.
+        `ema_decay=d`: a float32 moving average of the trained weights in `flat_ema`, updated inside the AdamW kernel after every step
+        that is taken (`oard_adamw_step_ema`; `d` is the weight of the old average, as in `DDPMTrainer`)."""
+        if not isinstance(confidence, Confidence) or not confidence.trainable:
+            raise ValueError("ConfidenceTrainer needs a Confidence module built with trainable=True")
+        self.confidence = confidence
+        self.classification, self.target_key, self.clip_grad = bool(classification), target_key, bool(clip_grad)
+        P = confidence._train_params()
+        self.names: List[str] = list(P)
+        self.params: List[Tensor] = list(P.values())
+        dev = self.params[0].device
+        if dev.type != "cuda" or any(p.dtype != torch.float32 or p.device != dev for p in self.params):
+            raise ValueError("ConfidenceTrainer needs float32 parameters on one ROCm device")
+        self.n_params = sum(p.numel() for p in self.params)
+        # the parameters the confidence forward uses become views of ONE flat buffer, their gradients views of ONE flat bucket; the
+        # tensors the forward never uses (confidence.CONF_UNUSED_PREFIXES) stay outside: no gradient, no weight decay, no step.
+        # Every view starts on a 16-byte boundary - the readout kernels read the weight rows four floats at a time -; the up to three
+        # floats in front of it are zero in every buffer and stay zero (AdamW of a zero weight under a zero gradient)
+        starts, n = [], 0
+        for p in self.params:
+            starts.append(n)
+            n = (n + p.numel() + 3) // 4 * 4
+        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.flat_param = torch.zeros(n, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            for p, off in zip(self.params, starts):
+                end = off + p.numel()
+                self.flat_param[off:end].copy_(p.reshape(-1))
+                p.data = self.flat_param[off:end].view_as(p)
+                p.grad = self.flat_grad[off:end].view_as(p)
+        confidence.grad_inplace = True                         # compute_loss(...)[0].backward() lands in the bucket as well
+        self._dests = {id(p): p.grad for p in self.params}
+        self.exp_avg = torch.zeros_like(self.flat_param)
+        self.exp_avg_sq = torch.zeros_like(self.flat_param)
+        self.max_exp_avg_sq = torch.zeros_like(self.flat_param)
+        self.opt_step = 0
+        self.skipped_steps = 0
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1] (got {ema_decay!r})")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.flat_ema = None if ema_decay is None else self.flat_param.detach().clone()
+        self.opt_config = dict(DEFAULT_OPTIMIZER, **(optimizer_config or {}))
+        # what configure_optimizers returns (pl_trainer.py:488-499): its param_groups[0] is read at EVERY step, so a scheduler attached
+        # to it takes effect; the moments live in the flat buffers here (state_dict)
+        self.optimizer = torch.optim.AdamW(self.params, **self.opt_config)
+        if self.clip_grad:                                     # pl_trainer.py:465-468
+            self.gradnorm_queue = Queue()
+            self.gradnorm_queue.add(3000)
+
+    # ---- resume ---------------------------------------------------------------------------------------------------------------------
+    def state_dict(self) -> Dict:
+        """What a bit-identical continuation needs besides the module's own state_dict(): the flat AdamW moments, the step counter, the
+        optimiser's hyper-parameters, the clipping history, the skipped-step counter (and the average, if one is kept)."""
+        sd: Dict = {"names": list(self.names), "skipped_steps": int(self.skipped_steps), "opt_step": int(self.opt_step),
+                    "gradnorm_queue": list(self.gradnorm_queue.items) if self.clip_grad else None,
+                    "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.optimizer.param_groups]}
+        for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"):
+            sd[k] = getattr(self, k).detach().clone()
+        if self.flat_ema is not None:
+            sd["ema_decay"], sd["ema"] = float(self.ema_decay), self.flat_ema.detach().clone()
+        return sd
+
+    def load_state_dict(self, sd: Dict) -> None:
+        if list(sd["names"]) != list(self.names):
+            raise ValueError("trainer state belongs to a different parameter list")
+        self.skipped_steps, self.opt_step = int(sd["skipped_steps"]), int(sd["opt_step"])
+        if self.clip_grad and sd.get("gradnorm_queue") is not None:
+            self.gradnorm_queue.items = [float(x) for x in sd["gradnorm_queue"]]
+        for g, saved in zip(self.optimizer.param_groups, sd["param_groups"]):
+            g.update(saved)
+        with torch.no_grad():
+            for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"):
+                getattr(self, k).copy_(sd[k].to(self.flat_param.device))
+            if self.flat_ema is not None and sd.get("ema") is not None:
+                self.ema_decay = float(sd.get("ema_decay", self.ema_decay))
+                self.flat_ema.copy_(sd["ema"].to(self.flat_ema.device))
+
+    # ---- loss -----------------------------------------------------------------------------------------------------------------------
+    def _targets(self, res, dev) -> Tensor:
+        return res[self.target_key].detach().to(device=dev, dtype=torch.float32).reshape(-1)
+
+    def _loss_and_metrics(self, logits: Tensor, y: Tensor) -> Tuple[Tensor, List[str], Tensor]:
+        """-> (loss, metric names, metric values [len(names)]) on the device; pl_trainer.py:564-584."""
+        x = logits.reshape(-1)
+        if self.classification:
+            p = torch.sigmoid(x)
+            # nn.BCELoss's expression (log terms clamped at -100) from element-wise ops: torch's own BCE kernel asserts 0 <= p <= 1 on
+            # the device, which a NaN prediction fails - and the step has to SKIP on a NaN, not abort the process
+            loss = -(y * torch.log(p).clamp(min=-100.0) + (1.0 - y) * torch.log(1.0 - p).clamp(min=-100.0)).mean()
+            hit, pos = p >= 0.5, y >= 0.5
+            tp = (hit & pos).sum().float()
+            fp, fn = (hit & ~pos).sum().float(), (~hit & pos).sum().float()
+            zero = torch.zeros((), device=x.device)
+            prec = torch.where(tp + fp > 0, tp / (tp + fp).clamp(min=1), zero)              # torchmetrics: 0 where undefined
+            f1 = torch.where(2 * tp + fp + fn > 0, 2 * tp / (2 * tp + fp + fn).clamp(min=1), zero)
+            return loss, ["acc", "precision", "F1", "mean"], torch.stack([(hit == pos).float().mean(), prec, f1, p.round().mean()])
+        loss = torch.nn.functional.mse_loss(x, y)
+        return loss, ["MAE", "mean"], torch.stack([(x - y).abs().mean(), x.mean()])
+
+    def compute_loss(self, batch) -> Tuple[Tensor, Dict[str, float]]:
+        """`ConfModule.compute_loss` (pl_trainer.py:554-585) -> (loss, info).  Under autograd the loss carries the module's
+        `ConfidenceFunction`; the logged metrics cost one host read."""
+        representations, res = batch
+        logits = self.confidence.forward(representations, res["condition"])
+        loss, names, vals = self._loss_and_metrics(logits, self._targets(res, logits.device))
+        return loss, dict(zip(names, vals.detach().tolist()))
+
+    # ---- the step -------------------------------------------------------------------------------------------------------------------
+    def _forward_backward(self, batch) -> Tuple[Tensor, List[str], Tensor]:
+        """Training-mode forward, closed-form cotangent, reverse sweep into the bucket -> (loss, metric names, metric values)."""
+        representations, res = batch
+        conf = self.confidence
+        dev = self.flat_grad.device
+        L = _capi.lib()
+        masks, sizes = [r["mask"] for r in representations], [r["size"] for r in representations]
+
+        def build():          # no edge list: the kernels walk the implicit complete graph, and there is no caller's list to verify
+            return _Layout(torch.cat(masks).to(dev), None, get_n_frag_switch([s.to(dev) for s in sizes]))
+        lay = conf._layout_cache.lookup(tuple(masks) + tuple(sizes), (str(dev), "train"), build)
+        xh = [torch.cat([r[f] for f in FEATURE_MAPPING], dim=1) for r in representations]
+        with torch.cuda.device(dev), torch.no_grad():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            cfg = conf._config()
+            _capi.check(L.oard_supported(C.byref(cfg)), "oard_supported (hidden_channels/num_radial not built)")
+            packed = conf._get_packed(cfg, stream)
+            topo = conf._get_train_topology(cfg, None, lay.n_frag_switch, lay.combined_mask, stream)
+            conf._check_train_topology(topo)
+            xs, tt, t_scalar, cond = conf._inputs(topo, xh, conf._zero_time(dev), res["condition"], dev, detach=True)
+            logits, state = conf._run_forward_train_conf(cfg, topo, packed, xs, tt, t_scalar, cond, stream, reuse_tape=True)
+            y = self._targets(res, dev)
+            if y.numel() != logits.numel():
+                raise _capi.OardError(f"{y.numel()} targets for {logits.numel()} reactions")
+            loss, names, vals = self._loss_and_metrics(logits, y)
+            B = logits.numel()
+            dlogits = (torch.sigmoid(logits) - y) / B if self.classification else 2.0 * (logits - y) / B
+            conf.backward_sweep(state, dlogits, self._dests, stream)
+        return loss, names, vals
+
+    def _adamw(self, gscale: float) -> None:
+        o = self.optimizer.param_groups[0]
+        dev = self.flat_grad.device
+        args = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(), float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]),
+                float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), self.opt_step, 1 if o.get("amsgrad", False) else 0,
+                float(gscale))
+        entry = "oard_adamw_step"
+        if self.flat_ema is not None:
+            entry, args = entry + "_ema", args + (self.flat_ema.data_ptr(), self.ema_decay)
+        with torch.cuda.device(dev):
+            _capi.check(getattr(_capi.lib(), entry)(*args, torch.cuda.current_stream(dev).cuda_stream), entry)
+        self.confidence.invalidate_packed()              # the weights changed behind torch's version counters
+
+    def training_step(self, batch) -> Dict[str, float]:
+        """One step; -> info: `loss`, `skipped`, the logged metrics of `compute_loss`, and with clipping `grad_norm` / `max_grad_norm`.
+        A non-finite loss, gradient or network output skips the step as `DDPMTrainer.training_step` does: weights, moments, step
+        count and clipping history untouched, `skipped_steps` counts it, `info["skipped"] = 1`."""
+        conf = self.confidence
+        conf.reset_nan_seen()
+        self.flat_grad.zero_()
+        loss, names, vals = self._forward_backward(batch)
+        norm = torch.linalg.vector_norm(self.flat_grad, 2.0)
+        bad = (~torch.isfinite(norm + loss)).to(torch.float32)
+        if conf.nan_seen is not None:
+            bad = bad + (conf.nan_seen[0] != 0).to(torch.float32)
+        stats = torch.cat([norm.reshape(1), bad.reshape(1), loss.reshape(1), vals]).tolist()          # the one host sync
+        grad_norm, flag = stats[0], stats[1]
+        info: Dict[str, float] = dict(zip(names, stats[3:]))
+        skipped = flag != 0 or not math.isfinite(grad_norm)
+        if skipped:
+            self.skipped_steps += 1
+            print(f"Warning: non-finite loss / gradient / network output: step skipped ({self.skipped_steps} so far)")
+            if self.clip_grad:
+                info["grad_norm"], info["max_grad_norm"] = grad_norm, float("nan")
+        else:
+            gscale = 1.0
+            if self.clip_grad:                                 # pl_trainer.py:642-669, the factor folded into the optimiser kernel
+                max_norm = CLIP_MEAN_FACTOR * self.gradnorm_queue.mean() + CLIP_STD_FACTOR * self.gradnorm_queue.std()
+                if grad_norm > max_norm:
+                    gscale = max_norm / (grad_norm + 1e-6)
+                    self.gradnorm_queue.add(float(max_norm))
+                    print(f"Clipped gradient with value {grad_norm:.1f} while allowed {max_norm:.1f}")
+                else:
+                    self.gradnorm_queue.add(grad_norm)
+                info["grad_norm"], info["max_grad_norm"] = grad_norm, max_norm
+            self.opt_step += 1
+            self._adamw(gscale)
+        info["loss"] = stats[2]
+        info["skipped"] = int(skipped)
+        return info
+

@@ -8,9 +8,18 @@ It is the denoiser's LEFTNet trunk with `for_conf=True` - the node scalars behin
 EquiUpdate, then `k_conf_readout` (csrc/oard_conf.h).  The module IS an `EGNNDynamics` as far as parameters, weight packing, topology
 cache and call buffers go; the twelve `readout.*` tensors are read by the kernel where they lie.
 
-INFERENCE ONLY.  There is no backward pass through the readout: the parameters are created with `requires_grad=False`, and a call with
-autograd enabled on a parameter that requires grad raises `NotImplementedError`.  Training the confidence model stays with the
-reference; its checkpoints load here (`checkpoint.load_confidence_checkpoint`)."""
+FROZEN BY DEFAULT.  `Confidence(...)` is the inference module: the parameters are created with `requires_grad=False`, and a call with
+autograd enabled on a parameter that was switched to require grad by hand raises `NotImplementedError`.  The reference's checkpoints
+load here (`checkpoint.load_confidence_checkpoint`).
+
+TRAINING: `Confidence(..., trainable=True)`.  The parameters require grad, and `_forward` / `forward` under autograd run
+`oard_confidence_forward_train` - the training-mode trunk with its tape, the same readout kernel - and return logits whose `grad_fn`
+is `ConfidenceFunction`.  Its backward is `oard_confidence_tail_backward` (csrc/oard_conf_bwd.h: the adjoint of mean pool + GatedMLP,
+float64 behind float32 loads, which seeds the cotangent of the final node scalars and accumulates the twelve readout gradients) and
+then the denoiser's own reverse sweep, unchanged: `training.Sweep.layer(l)` for l = L-1 .. 0 and `Sweep.init()`.  The tensors the
+reference's autograd leaves without a gradient under for_conf (`CONF_UNUSED_PREFIXES`: the output head, the decoders and the two
+modules no forward uses) get none here either.  Under `torch.no_grad()` a trainable module takes the inference entry: the same bits
+as a frozen one.  `conf_trainer.ConfidenceTrainer` is the reference's `ConfModule` step on top of this."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,6 +34,9 @@ from .graph_tools import get_edges_index, get_mask_for_frag, get_n_frag_switch
 from .spec import READOUT_NAMES, confidence_state_spec
 
 FEATURE_MAPPING = ["pos", "one_hot", "charge"]                              # confidence.py:18
+#: parameters the reference's autograd leaves at `.grad is None` under for_conf (leftnet.py:875-876 returns before the output head;
+#: the wrapper's decoders are never called, confidence.py:82-163), besides the two modules no forward uses
+CONF_UNUSED_PREFIXES = ("model.embedding_out.", "model.out_pos.", "decoders.", "model.distance_embedding.", "model.last_layer.")
 
 
 class _Layout:
@@ -48,6 +60,44 @@ def rank_candidates(scores: Tensor, n_reactions: int) -> Tuple[Tensor, Tensor]:
     return order[:, 0], order
 
 
+class ConfidenceFunction(torch.autograd.Function):
+    """logits = Confidence._forward(...) with the HIP training-mode forward and the reverse sweep as backward.  Inputs after the fixed
+    arguments: the xh tensors, then every parameter the forward uses (`Confidence._train_params`), so that autograd routes their
+    gradients.  `conf.grad_inplace` as for `training.DynamicsFunction`: the sweep accumulates into the existing `.grad` tensors and
+    autograd receives None."""
+
+    @staticmethod
+    def forward(ctx, conf, run_forward, n_obj, *tensors):
+        logits, state = run_forward()
+        ctx.conf, ctx.state, ctx.n_obj = conf, state, n_obj
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        conf, st = ctx.conf, ctx.state
+        dev = st.xh[0].device
+        P = conf._train_params()
+        if conf.grad_inplace:
+            for n, p in P.items():
+                if p.grad is None:
+                    p.grad = torch.zeros_like(p)
+                if p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
+                    raise _capi.OardError(f"grad_inplace needs contiguous float32 .grad tensors ({n})")
+            dests = {id(p): p.grad for p in P.values()}
+            out = {}
+        else:
+            flat = torch.zeros(sum(p.numel() for p in P.values()), dtype=torch.float32, device=dev)
+            out, off = {}, 0
+            for n, p in P.items():
+                out[n] = flat[off: off + p.numel()].view_as(p)
+                off += p.numel()
+            dests = {id(p): out[n] for n, p in P.items()}
+        with torch.cuda.device(dev), torch.no_grad():
+            conf.backward_sweep(st, dlogits, dests, torch.cuda.current_stream(dev).cuda_stream)
+        ctx.state = None
+        return (None, None, None) + (None,) * ctx.n_obj + tuple(out.get(n) for n in P)
+
+
 class Confidence(EGNNDynamics):
     _for_conf = True
 
@@ -64,6 +114,7 @@ class Confidence(EGNNDynamics):
         device: torch.device = torch.device("cuda"),
         enforce_same_encoding: Optional[List] = None,
         source: Optional[Dict] = None,
+        trainable: bool = False,
         **kwargs,
     ) -> None:
         model_config.update({"for_conf": True})                             # confidence.py:54-56
@@ -71,8 +122,9 @@ class Confidence(EGNNDynamics):
                          device, enforce_same_encoding, source=source)
         full = confidence_state_spec(model_config, node_nfs, condition_nf, pos_dim, True)
         self._create_tensors({name: full[name] for name in READOUT_NAMES}, device)      # confidence.py:73-80
-        for p in self.parameters():                                         # inference only: nothing here can be trained
-            p.requires_grad_(False)
+        self.trainable = bool(trainable)
+        for p in self.parameters():                                         # frozen unless built to be trained (module docstring)
+            p.requires_grad_(self.trainable)
         self.nan_check = "async"                                            # no host read in a call; the flag stays in `last_status`
         self._readout_slots = None
         self._layout_cache = _TensorKeyCache(8)                             # by the identity of the masks / sizes (forward)
@@ -109,10 +161,10 @@ class Confidence(EGNNDynamics):
         whose `combined_mask` value is b."""
         if edge_attr is not None:
             raise NotImplementedError("edge attributes are not part of the LEFTNet path")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if train and not self.trainable:
             raise NotImplementedError("the MI355X Confidence model is inference only: a parameter requires grad and autograd is enabled, but "
-                                      "there is no backward pass through the readout (call under torch.no_grad(), or train the confidence "
-                                      "model with the reference and load its checkpoint)")
+                                      "this module was built frozen (call under torch.no_grad(), or build it with trainable=True)")
         dev = xh[0].device
         if dev.type != "cuda":
             raise _capi.OardError("Confidence needs tensors on a ROCm device (no CPU fallback)")
@@ -125,6 +177,8 @@ class Confidence(EGNNDynamics):
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             packed = self._get_packed(cfg, stream)
+            if train:
+                return self._forward_train_conf(cfg, packed, xh, edge_index, t, conditions, n_frag_switch, combined_mask, stream)
             topo = self._get_topology(cfg, edge_index, n_frag_switch, combined_mask, stream)
             if topo.handle is None:
                 raise NotImplementedError("edge_index is not the complete graph per reaction (get_edges_index(combined_mask, "
@@ -146,6 +200,68 @@ class Confidence(EGNNDynamics):
             self.last_status = status
             buffers.note(status)
         return conf.squeeze()
+
+    # ---- training (trainable=True) ------------------------------------------------------------------
+    def _train_params(self) -> Dict[str, Tensor]:
+        """Canonical name -> parameter for every distinct tensor the confidence forward uses, in state-dict order: the trunk without
+        `CONF_UNUSED_PREFIXES`, then the twelve readout tensors."""
+        P = {n: p for n, p in self._param_dict().items() if not n.startswith(CONF_UNUSED_PREFIXES)}
+        dev = next(iter(P.values())).device
+        P.update(zip(READOUT_NAMES, self._readout_tensors(dev)))
+        return P
+
+    def _check_train_topology(self, topo) -> None:
+        if topo.max_sample_id != topo.B - 1:
+            raise _capi.OardError(f"combined_mask must name the reactions 0 .. B-1 with none missing: {topo.B} reactions, "
+                                  f"largest id {topo.max_sample_id}")
+
+    def _run_forward_train_conf(self, cfg, topo, packed: Tensor, xs: List[Tensor], tt: Tensor, t_scalar: int, cond: Optional[Tensor],
+                                stream: int, reuse_tape: bool = False):
+        """oard_confidence_forward_train on prepared inputs -> (logits [B], TrainState); no autograd involved (ConfidenceTrainer calls
+        this directly and feeds the closed-form loss gradient to `backward_sweep`)."""
+        from . import training
+        L = _capi.lib()
+        dev = xs[0].device
+        buffers = self._call_buffers
+        conf = torch.empty(topo.B, dtype=torch.float32, device=dev)
+        ws = buffers.workspace(L.oard_workspace_bytes(C.byref(cfg), topo.handle), dev)
+        tape_bytes = L.oard_tape_bytes(C.byref(cfg), topo.handle)
+        tape = buffers.tape(tape_bytes, dev) if reuse_tape else torch.empty(tape_bytes, dtype=torch.uint8, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        rc = L.oard_confidence_forward_train(C.byref(cfg), topo.handle, packed.data_ptr(), _capi.ptr_array(self._readout_tensors(dev)),
+                                             _capi.ptr_array(xs), tt.data_ptr(), t_scalar, cond.data_ptr() if cond is not None else None,
+                                             conf.data_ptr(), ws.data_ptr(), ws.numel(), tape.data_ptr(), tape.numel(),
+                                             status.data_ptr(), stream)
+        _capi.check(rc, "oard_confidence_forward_train")
+        self.last_status = status
+        buffers.note(status)
+        return conf, training.TrainState(cfg, topo, training.Tape(cfg, topo, tape), xs, tt, bool(t_scalar), cond)
+
+    def backward_sweep(self, st, dlogits: Tensor, dests: Dict[int, Tensor], stream: int) -> None:
+        """The reverse sweep of one `_run_forward_train_conf`: d loss / d logit ([B], by reaction id) -> parameter gradients ACCUMULATED
+        into `dests` (id(param) -> tensor) for every parameter of `_train_params` that has an entry."""
+        from . import training
+        dev = st.xh[0].device
+        dconf = dlogits.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        if dconf.numel() != st.topo.B:
+            raise _capi.OardError(f"{dconf.numel()} logit cotangents for {st.topo.B} reactions")
+        readout = self._readout_tensors(dev)
+        training.backward_sweep(self, st, [], stream, dests, conf_tail=(readout, dconf, [dests.get(id(p)) for p in readout]))
+
+    def _forward_train_conf(self, cfg, packed: Tensor, xh: List[Tensor], edge_index: Tensor, t: Tensor, conditions: Tensor,
+                            n_frag_switch: Tensor, combined_mask: Tensor, stream: int) -> Tensor:
+        """Forward under autograd: the training-mode HIP forward (tape) wrapped in `ConfidenceFunction`.  An edge list that is not the
+        complete graph per reaction is refused when the topology is built (training.TrainTopology), as for the denoiser."""
+        dev = xh[0].device
+        topo = self._get_train_topology(cfg, edge_index, n_frag_switch, combined_mask, stream)
+        self._check_train_topology(topo)
+        xs, tt, t_scalar, cond = self._inputs(topo, xh, t, conditions, dev, detach=True)
+
+        def run_forward():
+            return self._run_forward_train_conf(cfg, topo, packed, xs, tt, t_scalar, cond, stream)
+
+        logits = ConfidenceFunction.apply(self, run_forward, len(self.node_nfs), *xs, *self._train_params().values())
+        return logits.squeeze()
 
     def _zero_time(self, dev) -> Tensor:
         if self._t0 is None or self._t0.device != dev:

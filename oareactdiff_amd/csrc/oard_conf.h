@@ -37,7 +37,8 @@ OARD_DEV double conf_dot4(float4 w, const double* x, double acc) {
 }
 
 // One dense layer of both branches: out[br][o] = SiLU(bias[o] + sum_i W[o][i] in[br][i]), o < H.  `shared_in`: both branches read in[0].
-OARD_DEV void conf_dense(const ConfReadout& w, int layer, int H, const double* in, bool shared_in, double* out) {
+// `pre` != nullptr (the backward kernel, oard_conf_bwd.h): the pre-activations are kept there as well.
+OARD_DEV void conf_dense(const ConfReadout& w, int layer, int H, const double* in, bool shared_in, double* out, double* pre = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, H4 = H >> 2;
     for (int r = 4 * wave; r < 2 * H; r += 4 * CONF_WAVES) {
         const int br = r >= H ? 1 : 0, o = r - br * H;
@@ -52,8 +53,38 @@ OARD_DEV void conf_dense(const ConfReadout& w, int layer, int H, const double* i
         a0 = wave_sum_f64(a0); a1 = wave_sum_f64(a1); a2 = wave_sum_f64(a2); a3 = wave_sum_f64(a3);
         if (lane < 4) {
             const double a = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
-            out[br * H + o + lane] = conf_silu(a + (double)w.p[6 * br + 2 * layer + 1][o + lane]);
+            const double z = a + (double)w.p[6 * br + 2 * layer + 1][o + lane];
+            out[br * H + o + lane] = conf_silu(z);
+            if (pre) pre[br * H + o + lane] = z;
         }
+    }
+}
+
+// Step 1: g[c] = mean over the rows n0 .. n1 - 1 of column c < H of s, in the fixed order described above.  `part`: [CONF_GROUPS][H] doubles
+// of scratch LDS.  Ends with a barrier: every thread may read g.
+OARD_DEV void conf_pool(const float* __restrict__ s, int H, int HP, int n0, int n1, double* part, double* g) {
+    const int j = threadIdx.x / CONF_COLS;
+    for (int c = threadIdx.x % CONF_COLS; c < H; c += CONF_COLS) {
+        double acc = 0.0;
+        for (int n = n0 + j; n < n1; n += CONF_GROUPS) acc += (double)s[(size_t)n * HP + c];
+        part[j * H + c] = acc;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < H; c += CONF_WAVES * 64)
+        g[c] = (((part[c] + part[H + c]) + part[2 * H + c]) + part[3 * H + c]) / (double)(n1 - n0);
+    __syncthreads();
+}
+
+// Step 2's last layer (H -> 1, no activation): wave 0 the value branch, wave 1 the gate branch; out[0] = v, out[1] = z.  The caller
+// puts a barrier behind it.
+OARD_DEV void conf_last(const ConfReadout& w, int H, const double* h2, double* out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave < 2) {
+        const float4* __restrict__ row = (const float4*)w.p[6 * wave + 4];
+        double acc = 0.0;
+        for (int i = lane; i < (H >> 2); i += 64) acc = conf_dot4(row[i], h2 + wave * H + 4 * i, acc);
+        acc = wave_sum_f64(acc) + (double)w.p[6 * wave + 5][0];
+        if (lane == 0) out[wave] = acc;
     }
 }
 
@@ -66,32 +97,12 @@ OARD_KERNEL __global__ __launch_bounds__(CONF_WAVES * 64) void k_conf_readout(To
     const int b = blockIdx.x;
     if (b >= tp.B) return;
     const int n0 = tp.sample_ptr[b], n1 = tp.sample_ptr[b + 1];
-    {
-        const int j = threadIdx.x / CONF_COLS;
-        double* part = h1;                                                  // [CONF_GROUPS][H]
-        for (int c = threadIdx.x % CONF_COLS; c < H; c += CONF_COLS) {
-            double acc = 0.0;
-            for (int n = n0 + j; n < n1; n += CONF_GROUPS) acc += (double)s[(size_t)n * HP + c];
-            part[j * H + c] = acc;
-        }
-        __syncthreads();
-        for (int c = threadIdx.x; c < H; c += CONF_WAVES * 64)
-            g[c] = (((part[c] + part[H + c]) + part[2 * H + c]) + part[3 * H + c]) / (double)(n1 - n0);
-    }
-    __syncthreads();
+    conf_pool(s, H, HP, n0, n1, h1, g);
     conf_dense(w, 0, H, g, true, h1);
     __syncthreads();
     conf_dense(w, 1, H, h1, false, h2);
     __syncthreads();
-    // layer 2 (H -> 1, no activation): wave 0 the value branch, wave 1 the gate branch
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (wave < 2) {
-        const float4* __restrict__ row = (const float4*)w.p[6 * wave + 4];
-        double acc = 0.0;
-        for (int i = lane; i < (H >> 2); i += 64) acc = conf_dot4(row[i], h2 + wave * H + 4 * i, acc);
-        acc = wave_sum_f64(acc) + (double)w.p[6 * wave + 5][0];
-        if (lane == 0) g[wave] = acc;          // (g is dead: layer 1 read h1, and every wave is past the barrier behind it)
-    }
+    conf_last(w, H, h2, g);                    // (g is dead: layer 1 read h1, and every wave is past the barrier behind it)
     __syncthreads();
     if (threadIdx.x == 0) {
         const float v = (float)(g[0] / (1.0 + exp(-g[1])));

@@ -25,10 +25,11 @@
 #include "oard_node_bwd.h"
 #include "oard_rows.h"
 #include "oard_conf.h"       // k_conf_readout: the Confidence model's pooled gated readout (oard_confidence_forward)
+#include "oard_conf_bwd.h"   // k_conf_readout_bwd, k_conf_wgrad: its adjoint (oard_confidence_tail_backward)
 #include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
-#define OARD_VERSION 2043      // + oard_confidence_forward (2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
+#define OARD_VERSION 2044      // + oard_confidence_forward_train, oard_confidence_tail_backward (2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
 // The first-generation kernels (weights straight from L2, one wave per 16 nodes: gcl_variant / equi_variant / node_variant 0) are the
 // A/B baseline of round 1 and a cross-check in tests/test_hip_parity.py::test_every_kernel_variant_is_parity_green; they are compiled
 // into experiment builds (-DOARD_EXPERIMENTS) only - a product library refuses those variants (oard_debug_option returns OARD_EINVAL).
@@ -538,8 +539,9 @@ static TapeOff make_tape(const oard_config* c, const TopoDev& td) {
 // buffer (the update is out of place), the edge kernels store their pre-activations, and the node state at the
 // layer boundaries is written straight into its tape slots (no copies).  Every launch shape comes from the plan (oard_plan.h), made here
 // once from the caller's copy of the options.
-// `conf` != NULL (oard_confidence_forward, inference only): the trunk stops behind the last layer's EquiUpdate - no output head, `out`
-// is not used - and the readout kernel (oard_conf.h) turns the final node scalars into one value per reaction, conf->out[id].
+// `conf` != NULL (oard_confidence_forward, and with a tape oard_confidence_forward_train): the trunk stops behind the last layer's
+// EquiUpdate - no output head, `out` is not used - and the readout kernel (oard_conf.h) turns the final node scalars (training: the
+// tape's S_IN[L]) into one value per reaction, conf->out[id].
 struct ConfHead { ConfReadout w; float* out; };
 template <class D>
 static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoPart* topo, const float* wb, const float* const* xh,
@@ -716,7 +718,6 @@ static int forward_impl(const FwdOptions& opt, const oard_config* c, const TopoP
         if (z.count > 0) LAUNCH(F_OTHER, k_zero_rows, z.count, 256, st, z);
     }
     if (conf) {
-        if (train) return OARD_EINVAL;
         ScopedLaunch sl_(F_OTHER, st);
         hipLaunchKernelGGL(k_conf_readout, dim3((unsigned)tp.B), dim3(CONF_WAVES * 64), 5 * D::H * sizeof(double), st, tp,
                            (const float*)s_at(c->num_layers), D::H, D::HP, conf->w, conf->out, status);
@@ -1568,19 +1569,26 @@ int oard_forward(const oard_config* c, const oard_topology* topo, const void* pa
     return forward_parts(c, topo, packed, xh, t, t_is_scalar, cond, out, ws, ws_bytes, status, stream, nullptr);
 }
 
+// what every confidence entry refuses: an unbuilt width pair, reaction ids other than 0 .. B - 1, a missing or misaligned readout tensor
+static int conf_head(const oard_config* c, const oard_topology* topo, const float* const* readout, float* conf_out, ConfHead* head) {
+    if (!config_ok(c) || !topo || !readout || !topo->ids_dense) return OARD_EINVAL;
+    for (int i = 0; i < 12; ++i) {          // (the kernels read the weight rows as float4)
+        if (!readout[i] || (i % 2 == 0 && ((uintptr_t)readout[i] & 15))) return OARD_EINVAL;
+        head->w.p[i] = readout[i];
+    }
+    head->out = conf_out;
+    return OARD_OK;
+}
+
 // Confidence._forward (oa_reactdiff/dynamics/confidence.py:82-163): the trunk up to the last layer's node scalars, then k_conf_readout
 // once per sub-batch on that sub-batch's stream.  conf_dev is indexed by the reactions' combined_mask values, so those must be
 // 0 .. B - 1 with none missing (what scatter_mean's output rows are in the reference).
 int oard_confidence_forward(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* readout,
                             const float* const* xh, const float* t, int t_is_scalar, const float* cond, float* conf_out,
                             void* ws, size_t ws_bytes, int32_t* status, oard_stream_t stream) {
-    if (!config_ok(c) || !topo || !readout || !conf_out || !topo->ids_dense) return OARD_EINVAL;
     ConfHead head;
-    for (int i = 0; i < 12; ++i) {          // (the kernel reads the weight rows as float4)
-        if (!readout[i] || (i % 2 == 0 && ((uintptr_t)readout[i] & 15))) return OARD_EINVAL;
-        head.w.p[i] = readout[i];
-    }
-    head.out = conf_out;
+    const int rc = conf_out ? conf_head(c, topo, readout, conf_out, &head) : OARD_EINVAL;
+    if (rc != OARD_OK) return rc;
     return forward_parts(c, topo, packed, xh, t, t_is_scalar, cond, nullptr, ws, ws_bytes, status, stream, &head);
 }
 
@@ -1762,11 +1770,12 @@ int oard_tape_entry(const oard_config* c, const oard_topology* topo, int which, 
     return OARD_OK;
 }
 
-int oard_forward_train(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* xh,
-                       const float* t, int t_is_scalar, const float* cond, float* const* out, void* ws, size_t ws_bytes,
-                       void* tape, size_t tape_bytes, int32_t* status, oard_stream_t stream) {
+// the training-mode call of oard_forward_train (`conf` NULL) and oard_confidence_forward_train: validation, poisoning, one sub-batch
+static int forward_train_impl(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* xh,
+                              const float* t, int t_is_scalar, const float* cond, float* const* out, void* ws, size_t ws_bytes,
+                              void* tape, size_t tape_bytes, int32_t* status, oard_stream_t stream, const ConfHead* conf) {
     topo_touch(topo, (hipStream_t)stream);
-    if (!config_ok(c) || !topo || !packed || !xh || !out || !ws || !tape || !status) return OARD_EINVAL;
+    if (!config_ok(c) || !topo || !packed || !xh || (!out && !conf) || !ws || !tape || !status) return OARD_EINVAL;
     if (topo->n_parts != 1 || c->n_obj != topo->n_obj) return OARD_EINVAL;
     if (c->condition_time && !t) return OARD_EINVAL;
     if (c->condition_nf > 0 && !cond) return OARD_EINVAL;
@@ -1779,8 +1788,26 @@ int oard_forward_train(const oard_config* c, const oard_topology* topo, const vo
     }
     int rc = OARD_EINVAL;
     DISPATCH_DIMS(c, rc = forward_impl<D>(FwdOptions(g_fwd), c, &topo->parts[0], (const float*)packed, xh, t, t_is_scalar, cond, out,
-                                          (char*)ws + topo->parts[0].ws_off, (char*)tape, (int*)status, st));
+                                          (char*)ws + topo->parts[0].ws_off, (char*)tape, (int*)status, st, conf));
     return rc;
+}
+
+int oard_forward_train(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* xh,
+                       const float* t, int t_is_scalar, const float* cond, float* const* out, void* ws, size_t ws_bytes,
+                       void* tape, size_t tape_bytes, int32_t* status, oard_stream_t stream) {
+    if (!out) return OARD_EINVAL;
+    return forward_train_impl(c, topo, packed, xh, t, t_is_scalar, cond, out, ws, ws_bytes, tape, tape_bytes, status, stream, nullptr);
+}
+
+// Confidence._forward under autograd: oard_confidence_forward's trunk in training mode (tape written, one sub-batch), the same readout
+// launch on the tape's S_IN[L].  Its backward starts with oard_confidence_tail_backward.
+int oard_confidence_forward_train(const oard_config* c, const oard_topology* topo, const void* packed, const float* const* readout,
+                                  const float* const* xh, const float* t, int t_is_scalar, const float* cond, float* conf_out,
+                                  void* ws, size_t ws_bytes, void* tape, size_t tape_bytes, int32_t* status, oard_stream_t stream) {
+    ConfHead head;
+    const int rc = conf_out ? conf_head(c, topo, readout, conf_out, &head) : OARD_EINVAL;
+    if (rc != OARD_OK) return rc;
+    return forward_train_impl(c, topo, packed, xh, t, t_is_scalar, cond, nullptr, ws, ws_bytes, tape, tape_bytes, status, stream, &head);
 }
 
 }  // extern "C"
@@ -2236,6 +2263,44 @@ int oard_train_tail_backward(const oard_config* c, const oard_topology* topo, co
     if (rc == OARD_OK) rc = wgq_flush();
     x.join();                   // (a small stage; its operand buffers are reused by nothing until the next sweep, but tests read its gradients right away)
     return rc;
+}
+
+// The confidence counterpart of oard_train_tail_backward: the adjoint of mean pool + GatedMLP (oard_conf_bwd.h) seeds (ds, dvec) of the
+// final node state; oard_train_layer_backward / oard_train_init_backward follow unchanged.  Both launches run on the caller's stream.
+// Scratch: B * CONF_OPS(H) doubles at the start of the sweep's scratch - 72 H + 16 bytes per reaction, while the per-layer region that
+// starts there holds more than 22 node buffers of N * HP * 4 bytes (TrainWs: hid .. cvec) and B <= N; checked all the same.
+int oard_confidence_tail_backward(const oard_config* c, const oard_topology* topo, const void* tape, const float* const* readout,
+                                  const float* dconf, float* ds, float* dvec, float* const* readout_grads, void* scratch,
+                                  size_t scratch_bytes, oard_stream_t stream) {
+    topo_touch(topo, (hipStream_t)stream);
+    ConfHead head;
+    if (!dconf || !ds || !dvec || !readout_grads || !tape || !scratch) return OARD_EINVAL;
+    int rc = conf_head(c, topo, readout, nullptr, &head);
+    if (rc != OARD_OK) return rc;
+    if (topo->n_parts != 1) return OARD_EINVAL;
+    const TopoDev& tp = topo->parts[0].d;
+    const RDims r(c->hidden, c->num_radial);
+    const size_t total = oard_train_scratch_bytes(c, topo), need = (size_t)tp.B * CONF_OPS(r.H) * sizeof(double);
+    const size_t lds = CONF_BWD_LDS(r.H) * sizeof(double);
+    if (scratch_bytes < total || need > total) return OARD_ENOMEM;
+    if (lds > 64 * 1024 || ((uintptr_t)scratch & 7)) return OARD_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (g_poison) HIP_TRY(hipMemsetAsync(scratch, 0xFF, total, st));       // first call of a sweep
+    const float* s_L = (const float*)((const char*)tape + make_tape(c, tp).s_in[c->num_layers]);
+    ConfReadoutGrads gr;
+    for (int i = 0; i < 12; ++i) gr.p[i] = readout_grads[i];
+    const long long elems = 2 * (2LL * r.H * r.H + 3LL * r.H + 1);
+    {
+        ScopedLaunch sl_(F_OTHER, st);
+        hipLaunchKernelGGL(k_conf_readout_bwd, dim3((unsigned)tp.B), dim3(CONF_WAVES * 64), lds, st, tp, s_L, r.H, r.HP, head.w, dconf, ds,
+                           dvec, (double*)scratch);
+    }
+    {
+        ScopedLaunch sl_(F_WGRAD, st);
+        hipLaunchKernelGGL(k_conf_wgrad, dim3((unsigned)cdiv(elems, 256)), dim3(256), 0, st, tp.B, r.H, (const double*)scratch, gr);
+    }
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
 }
 
 int oard_train_init_backward(const oard_config* c, const oard_topology* topo, const void* packed, const void* packed_bwd,

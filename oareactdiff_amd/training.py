@@ -206,10 +206,13 @@ class Sweep:
     read - behind all of its own).
     `dests` (id(param) -> tensor): accumulate INTO these tensors (e.g. the `.grad` views of a flat bucket); None: accumulate into a fresh
     zero-filled flat buffer, `self.out` = {canonical name: view}.  `buffers`: the per-call buffer set whose scratch the sweep uses - the one
-    its forward ran on (None: the module's own)."""
+    its forward ran on (None: the module's own).
+    `conf_tail` = (readout tensors [12], dconf [B], readout gradient destinations [12], None entries skipped): the sweep of a
+    `Confidence` forward (oard_confidence_forward_train) - `tail` is then oard_confidence_tail_backward, the adjoint of the pooled gated
+    readout, `grad_outs` is not used and `dests` is required (the caller knows which trunk tensors the confidence forward uses)."""
 
     def __init__(self, dyn, st: TrainState, grad_outs: List[Optional[Tensor]], stream: int, dests: Optional[Dict[int, Tensor]] = None,
-                 buffers=None):
+                 buffers=None, conf_tail=None):
         L = _capi.lib()
         self.L, self.st, self.stream = L, st, stream
         cfg, topo, tape = st.cfg, st.topo, st.tape
@@ -221,6 +224,9 @@ class Sweep:
         packed, pbwd = dyn._get_packed(cfg, stream), dyn._get_packed_bwd(cfg, stream)
         sc = (dyn._call_buffers if buffers is None else buffers).scratch(L.oard_train_scratch_bytes(C.byref(cfg), topo.handle), dev)
         self.out: Dict[str, Tensor] = {}
+        self.conf_tail = conf_tail
+        if conf_tail is not None and dests is None:
+            raise ValueError("a confidence sweep needs its gradient destinations")
         if dests is None:
             names = dyn._param_names()
             P = dyn._param_dict()
@@ -254,6 +260,13 @@ class Sweep:
         st.keepalive = (gos, ds, dvec, dew)
 
     def tail(self):
+        if self.conf_tail is not None:
+            readout, dconf, rgrads = self.conf_tail
+            _capi.check(self.L.oard_confidence_tail_backward(self.a[0], self.a[1], self.a[4], _capi.ptr_array(readout), dconf.data_ptr(),
+                                                             self.ds.data_ptr(), self.dvec.data_ptr(), _capi.ptr_array(rgrads),
+                                                             self.sc.data_ptr(), self.sc.numel(), self.stream),
+                        "oard_confidence_tail_backward")
+            return
         _capi.check(self.L.oard_train_tail_backward(*self.a, self.go, self.ds.data_ptr(), self.dvec.data_ptr(), self.params, self.grads,
                                                     self.sc.data_ptr(), self.sc.numel(), self.stream), "oard_train_tail_backward")
 
@@ -268,13 +281,13 @@ class Sweep:
 
 
 def backward_sweep(dyn, st: TrainState, grad_outs: List[Optional[Tensor]], stream: int,
-                   dests: Optional[Dict[int, Tensor]] = None, buffers=None) -> Dict[str, Tensor]:
+                   dests: Optional[Dict[int, Tensor]] = None, buffers=None, conf_tail=None) -> Dict[str, Tensor]:
     """d(loss)/d(parameter) for every parameter the forward uses, given d(loss)/d(out[k]).
     `dests` (id(param) -> tensor): accumulate INTO these tensors (e.g. the `.grad` views of a flat bucket) and return {};
-    None: accumulate into a fresh zero-filled flat buffer and return {canonical name: view}.  `buffers`: as for `Sweep`."""
+    None: accumulate into a fresh zero-filled flat buffer and return {canonical name: view}.  `buffers`, `conf_tail`: as for `Sweep`."""
     tm = _StageTimer()
     tm.mark("start")
-    sw = Sweep(dyn, st, grad_outs, stream, dests, buffers)
+    sw = Sweep(dyn, st, grad_outs, stream, dests, buffers, conf_tail)
     sw.tail()
     tm.mark("tail")
     for l in reversed(range(sw.NL)):

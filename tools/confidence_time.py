@@ -1,5 +1,6 @@
 """One Confidence call beside one denoiser call on the headline batch (B = 64 reactions x 3 objects x 23 atoms, production widths),
 both timed with HIP events on the same build:  python tools/confidence_time.py [--b 64] [--n 23] [--iters 20]
+--train: one `ConfidenceTrainer.training_step` beside one `DDPMTrainer.training_step` (host-sync, one micro-batch) on the same batch.
 Prints one JSON line (DESIGN.md quotes it)."""
 import argparse
 import json
@@ -29,14 +30,42 @@ def timed(fn, iters, warmup=5):
     return statistics.median(ms), min(ms)
 
 
+def train_mode(a, dev):
+    """One training step of either trainer on one fixed batch, alternating, three blocks each (wall time between HIP events: a step
+    ends with its host read)."""
+    from bench import make_training_batch
+    from oareactdiff_amd import ConfidenceTrainer, DDPMTrainer
+    cfg, node_nfs, cnf = dict(PRODUCTION_LEFTNET_CONFIG), [9, 9, 9], 1
+    reps, cond = make_training_batch(a.b, a.n, 100, dev)
+    labels = (torch.arange(a.b, device=dev) % 2).float()
+    dyn = EGNNDynamics(model_config=dict(cfg), fragment_names=["R", "TS", "P"], node_nfs=node_nfs, edge_nf=0, condition_nf=cnf, device=dev)
+    dyn.load_state_dict(synthetic_state_dict(state_spec(cfg, node_nfs, cnf), cfg), strict=True)
+    conf = Confidence(model_config=dict(cfg), fragment_names=["R", "TS", "P"], node_nfs=node_nfs, edge_nf=0, condition_nf=cnf, device=dev,
+                      trainable=True)
+    conf.load_state_dict(synthetic_state_dict(confidence_state_spec(cfg, node_nfs, cnf), cfg), strict=True)
+    ddpm = DDPMTrainer(dyn, norm_values=(1.0, 4.0, 10.0), pos_only=True)
+    ctr = ConfidenceTrainer(conf)
+    rounds = []
+    for _ in range(3):
+        rounds.append(timed(lambda: ddpm.training_step((reps, cond)), a.iters) +
+                      timed(lambda: ctr.training_step((reps, {"condition": cond, "rmsd": labels})), a.iters))
+    col = lambda i: [round(r[i], 4) for r in rounds]
+    print(json.dumps(dict(mode="train", batch=a.b, atoms_per_object=a.n, iters=a.iters, denoiser_step_ms_median=col(0),
+                          denoiser_step_ms_min=col(1), confidence_step_ms_median=col(2), confidence_step_ms_min=col(3),
+                          trained_parameters=dict(denoiser=int(ddpm.flat_grad.numel()), confidence=int(ctr.n_params)))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--b", type=int, default=64)
     ap.add_argument("--n", type=int, default=23)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--precision", default=None)
+    ap.add_argument("--train", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.train:
+        return train_mode(a, dev)
     cfg, node_nfs, cnf = dict(PRODUCTION_LEFTNET_CONFIG), [9, 9, 9], 1
     frag = [torch.full((a.b,), a.n, dtype=torch.long) for _ in range(3)]
     cm = torch.cat([get_mask_for_frag(f) for f in frag]).to(dev)
