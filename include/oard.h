@@ -538,8 +538,8 @@ int oard_ema_update(float* ema_dev, const float* param_dev, int64_t n, double em
 /* ---- validation metric: optimal-superposition RMSD per molecule ------------------------------------------------------------------
  * Replaces: the same-order Kabsch fit of rmsd_core (oa_reactdiff/analyze/rmsd.py:30-35, pymatgen's KabschMatcher), the chirality
  * handling of pymatgen_rmsd and the per-molecule loop of batch_rmsd (:54-100), which DDPMModule.eval_inplaint_batch logs
- * (trainer/pl_trainer.py:284-325).  NOT replaced: the permutation search over like atoms of rmsd_core's other branch (:36-51) - rows
- * are compared in the order given, an upper bound on the order-matched number.
+ * (trainer/pl_trainer.py:284-325).  Rows are compared in the order given, an upper bound on the order-matched number; the permutation
+ * search over like atoms of rmsd_core's other branch (:36-51) is oard_matched_rmsd below.
  * Segment g is rows seg_ptr[g] .. seg_ptr[g + 1] (seg_ptr_dev: n_segments + 1 ascending int32) of a_dev and b_dev: row-major float32
  * with row strides lda / ldb >= 3 in ELEMENTS, coordinates in the first three columns (the other columns are never read, so the
  * [n, node_nf] tensors of the samplers are passed as they are).  One wavefront per segment (csrc/oard_kabsch.h); float64 throughout:
@@ -558,6 +558,33 @@ int oard_kabsch_rmsd(const float* a_dev, int64_t lda, const float* b_dev, int64_
                      const int32_t* seg_ptr_dev, int64_t n_segments, int flags /* bit 0: allow reflection */,
                      float cap /* <= 0: none */, float* rmsd_dev, float* rot_dev /* or NULL */,
                      float* aligned_dev /* or NULL */, oard_stream_t stream);
+
+/* ---- validation metric with like atoms matched first ----------------------------------------------------------------------------------
+ * Replaces: the permutation search of rmsd_core (oa_reactdiff/analyze/rmsd.py:36-51) in front of the superposition above.  Defined as
+ *     M(a, b) = min over the permutations pi mapping every row of a to a row of b of the same species (and, with flags bit 0, over the
+ *               z-mirror image of b) of the optimal-superposition RMSD of a against b[pi].
+ * NOT replaced: pymatgen's genetic matcher and its `threshold`, and its Hungarian matcher's axis heuristics, which define no function
+ * of the inputs.  Per segment (csrc/oard_match.h, one wavefront each, float64, bitwise independent of the other segments):
+ *   status 0, exact:  the number of such permutations, prod c_s!, is below exact_limit (0 .. 10000; the reference's `< 1e4`; 0 turns the
+ *                     branch off): every one is evaluated and M returned.
+ *   status 1, search: otherwise; assignment (minimum cost per species block for |a_i - R b_j|^2, Jonker-Volgenant) and superposition
+ *                     alternate from five starts per chirality (the same-order fit and the four proper alignments of the principal
+ *                     axes) until the permutation repeats or 32 assignments were made; the smallest RMSD is returned:
+ *                     M <= result <= the same-order RMSD.
+ *   status 2: the species of a's and b's rows differ as multisets;  status 3: more than 256 rows;  status 4: a non-finite coordinate
+ *             (3 is checked first, then 4, then 2).  rmsd = cap if cap > 0, else NaN; rot / aligned NaN; perm the identity.
+ *   An empty segment gives NaN and status 0.
+ * Arguments as for oard_kabsch_rmsd, and: species_a_dev / species_b_dev, one int32 per row of a_dev / b_dev (species_b_dev NULL: the
+ * same as species_a_dev); perm_dev (or NULL): [rows] int32, perm[r] = the row of b_dev matched to row r of a_dev (an index into the whole
+ * array, inside r's segment); status_dev (or NULL): [n_segments] int32.  rot_dev as above; aligned_dev row r = rot (b_perm[r] - c_b) + c_a:
+ * b in a's frame AND in a's row order.  The RMSD is the residual of a pass over the rows with the kept permutation and map.
+ * OARD_EINVAL as for oard_kabsch_rmsd, and for a null species_a_dev or exact_limit outside 0 .. 10000. */
+int oard_matched_rmsd(const float* a_dev, int64_t lda, const float* b_dev, int64_t ldb,
+                      const int32_t* species_a_dev, const int32_t* species_b_dev /* or NULL */,
+                      const int32_t* seg_ptr_dev, int64_t n_segments, int flags /* bit 0: allow reflection */,
+                      float cap /* <= 0: none */, int exact_limit, float* rmsd_dev, float* rot_dev /* or NULL */,
+                      float* aligned_dev /* or NULL */, int32_t* perm_dev /* or NULL */, int32_t* status_dev /* or NULL */,
+                      oard_stream_t stream);
 
 /* The library's own streams of the current device(three non-blocking streams, chosen once per device so that each runs on a hardware
  * queue of its own beside the caller's stream - the runtime serves a process's streams from 4 queues): 0 = the training sweep's

@@ -29,7 +29,7 @@
 #include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
-#define OARD_VERSION 2044      // + oard_confidence_forward_train, oard_confidence_tail_backward (2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
+#define OARD_VERSION 2045      // + oard_matched_rmsd (2044: oard_confidence_forward_train, oard_confidence_tail_backward; 2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
 // The first-generation kernels (weights straight from L2, one wave per 16 nodes: gcl_variant / equi_variant / node_variant 0) are the
 // A/B baseline of round 1 and a cross-check in tests/test_hip_parity.py::test_every_kernel_variant_is_parity_green; they are compiled
 // into experiment builds (-DOARD_EXPERIMENTS) only - a product library refuses those variants (oard_debug_option returns OARD_EINVAL).
@@ -2216,6 +2216,7 @@ int oard_wgrad(const float* dY, int ldY, int ncY, int o_len, int o_pad, int MO, 
 #include "oard_train_stages.h"
 #include "oard_loss.h"
 #include "oard_kabsch.h"     // k_kabsch_rmsd: the validation metric (oard_kabsch_rmsd)
+#include "oard_match.h"      // k_matched_rmsd: the same with the atoms matched first (oard_matched_rmsd)
 extern "C" {
 
 // ---- the backward sweep through the C ABI (include/oard.h) ------------------------------------------------------------------------
@@ -2498,6 +2499,20 @@ int oard_kabsch_rmsd(const float* a, int64_t lda, const float* b, int64_t ldb, c
     if (n_segments == 0) return OARD_OK;
     LAUNCH(F_OTHER, k_kabsch_rmsd, n_segments, 64, (hipStream_t)stream, a, (long long)lda, b, (long long)ldb, seg_ptr, flags, cap, rmsd, rot,
            aligned);
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+// ---- the same with like atoms matched first (analyze/rmsd.py:36-51; oard_match.h) ---------------------------------------------------------
+int oard_matched_rmsd(const float* a, int64_t lda, const float* b, int64_t ldb, const int32_t* species_a, const int32_t* species_b,
+                      const int32_t* seg_ptr, int64_t n_segments, int flags, float cap, int exact_limit, float* rmsd, float* rot,
+                      float* aligned, int32_t* perm, int32_t* status, oard_stream_t stream) {
+    if (!a || !b || !species_a || !seg_ptr || !rmsd || n_segments < 0 || n_segments > 0x7fffffffLL || lda < 3 || ldb < 3 ||
+        exact_limit < 0 || exact_limit > MATCH_LIMIT)
+        return OARD_EINVAL;
+    if (n_segments == 0) return OARD_OK;
+    LAUNCH(F_OTHER, k_matched_rmsd, n_segments, 64, (hipStream_t)stream, a, (long long)lda, b, (long long)ldb, species_a, species_b, seg_ptr,
+           flags, cap, exact_limit, rmsd, rot, aligned, perm, status);
     HIP_TRY(hipGetLastError());
     return OARD_OK;
 }

@@ -2,7 +2,8 @@
 //
 // Replaces the same-order branch of the reference's RMSD (oa_reactdiff/analyze/rmsd.py:30-35: pymatgen's KabschMatcher) and its
 // chirality handling (:66-74: the z-mirrored structure is fitted too and the smaller RMSD kept), per molecule of a batch
-// (batch_rmsd, :78-100).  The permutation search of rmsd_core's other branch (:36-51) is NOT here: rows are compared in the order given.
+// (batch_rmsd, :78-100).  Rows are compared in the order given; the permutation search of rmsd_core's other branch (:36-51) is
+// k_matched_rmsd (csrc/oard_match.h), which builds on kabsch_rotation below.
 //
 // One wavefront per segment, no LDS, no scratch, no topology: a segment is rows seg_ptr[g] .. seg_ptr[g + 1] of two row-major float32
 // arrays whose first three columns are the coordinates (row strides lda / ldb in elements), so the [n, node_nf] tensors of the samplers
@@ -53,7 +54,8 @@ OARD_DEV void kabsch_rotate(double (&A)[4][4], double (&V)[4][4]) {
 }
 
 // S[i][j] = sum b_i a_j (centred) -> R (row-major) with R b ~ a: Horn (1987), the quaternion of the largest eigenvalue of N(S).
-OARD_DEV void kabsch_rotation(const double (&S)[3][3], double (&R)[3][3]) {
+// Returns that eigenvalue (k_matched_rmsd ranks permutations by it, csrc/oard_match.h).
+OARD_DEV double kabsch_rotation(const double (&S)[3][3], double (&R)[3][3]) {
     double A[4][4], V[4][4];
     A[0][0] = S[0][0] + S[1][1] + S[2][2];
     A[1][1] = S[0][0] - S[1][1] - S[2][2];
@@ -87,6 +89,7 @@ OARD_DEV void kabsch_rotation(const double (&S)[3][3], double (&R)[3][3]) {
     R[0][0] = w * w + x * x - y * y - z * z; R[0][1] = 2.0 * (x * y - w * z); R[0][2] = 2.0 * (x * z + w * y);
     R[1][0] = 2.0 * (x * y + w * z); R[1][1] = w * w - x * x + y * y - z * z; R[1][2] = 2.0 * (y * z - w * x);
     R[2][0] = 2.0 * (x * z - w * y); R[2][1] = 2.0 * (y * z + w * x); R[2][2] = w * w - x * x - y * y + z * z;
+    return lam;
 }
 
 OARD_KERNEL __global__ __launch_bounds__(64) void k_kabsch_rmsd(const float* __restrict__ a, long long lda, const float* __restrict__ b,

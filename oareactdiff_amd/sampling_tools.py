@@ -38,10 +38,17 @@ def assemble_sample_inputs(atoms: List[str], device: torch.device = torch.device
     return out
 
 
-def write_single_xyz(xyzfile: str, natoms: int, out: torch.Tensor) -> None:
+def write_single_xyz(xyzfile: str, natoms: int, out: torch.Tensor, perm=None) -> None:
     """One molecule: rows of `out` are [x, y, z, one-hot(5), charge, ...]; element from column 8
-    (sampling_tools.py:111-127)."""
+    (sampling_tools.py:111-127).  `perm` (optional, a permutation of `out`'s rows): the rows are written in the order `out[perm]` -
+    with this molecule's part of `metrics.matched_rmsd(..., return_perm=True)`, less the index of the molecule's first row, that is
+    the atom order of the structure it was matched to."""
     rows = out[:, :9].detach().cpu()
+    if perm is not None:
+        perm = torch.as_tensor(perm).detach().cpu().long().reshape(-1)
+        if sorted(perm.tolist()) != list(range(rows.shape[0])):
+            raise ValueError("perm must be a permutation of the molecule's rows")
+        rows = rows[perm]
     xyz = rows[:, :3].numpy()
     charge = rows[:, 8].long().tolist()
     with open(xyzfile, "w") as fo:
@@ -51,17 +58,20 @@ def write_single_xyz(xyzfile: str, natoms: int, out: torch.Tensor) -> None:
 
 
 def write_tmp_xyz(fragments_nodes, out_samples, idx=(0,), prefix: str = "gen", localpath: str = "tmp",
-                  ex_ind: int = 0) -> List[str]:
+                  ex_ind: int = 0, perm=None) -> List[str]:
     """`{localpath}/{prefix}_{sample + ex_ind}_{react|ts|prod}.xyz` for every sample of the objects in `idx`
-    (sampling_tools.py:130-149).  Returns the paths written."""
+    (sampling_tools.py:130-149).  Returns the paths written.  `perm` (optional): object -> `[rows]` indices into that object's rows as
+    `metrics.matched_rmsd(..., return_perm=True)` returns them (every molecule's indices inside the molecule); the molecules of that
+    object are written in the matched order.  Pass `out_samples` with the aligned coordinates put in to write the superposed structure."""
     sizes = [int(n) for n in torch.as_tensor(fragments_nodes[0]).tolist()]
     paths = []
     for k in idx:
         rows = out_samples[k].detach().cpu()
+        pk = None if perm is None or perm.get(k) is None else torch.as_tensor(perm[k]).detach().cpu().long().reshape(-1)
         start = 0
         for j, n in enumerate(sizes):
             path = os.path.join(localpath, f"{prefix}_{j + ex_ind}_{_OBJECT_TAG[k]}.xyz")
-            write_single_xyz(path, n, rows[start:start + n])
+            write_single_xyz(path, n, rows[start:start + n], None if pk is None else pk[start:start + n] - start)
             paths.append(path)
             start += n
     return paths

@@ -323,7 +323,7 @@ class DDPMTrainer:
     # pl_trainer.py:284-325
     def eval_inpaint_batch(self, batch, resamplings: int = 5, jump_length: int = 5, frag_fixed: Sequence[int] = (0, 2), idx: int = 1,
                            weights: str = "live", noise_schedule: str = "polynomial_2", timesteps: Optional[int] = None,
-                           cap: Optional[float] = 1.0, noise_fn=None) -> Tuple[float, float]:
+                           cap: Optional[float] = 1.0, noise_fn=None, match_order: bool = False) -> Tuple[float, float]:
         """The validation metric of the reference's `eval_inplaint_batch` (pl_trainer.py:284-325, logged by training_step / _shared_eval):
         object `idx` (the transition state) of every reaction of `batch` is inpainted with the objects `frag_fixed` (reactant, product)
         held fixed, and the (mean, median) RMSD between the generated and the true structure is returned.
@@ -340,7 +340,10 @@ class DDPMTrainer:
         layout is otherwise read from the device `size` tensors once per new layout.  A NaN network output does not raise: the loop
         warns, and the affected reactions are the non-finite ones above.
         The call changes no weight, no optimiser or EMA state, and neither the module's `training` flag nor its `nan_check`.
-        RMSD as in `oareactdiff_amd.metrics`: atoms matched in the order given - the reference's permutation search is not implemented."""
+        RMSD as in `oareactdiff_amd.metrics.batch_rmsd`: `match_order=False` compares atoms in the order given (an inpainted transition
+        state keeps the order of the fixed reactant and product); `match_order=True` matches like atoms first, as the reference's
+        `rmsd_core` does, in the same one launch and with the same host reads - never a larger number.  A generated atom whose charge
+        column does not truncate to the true atomic number makes the species lists differ: that reaction counts `cap`."""
         from .metrics import batch_rmsd
         from .sampler import DiffusionSampler
         if weights not in ("live", "ema"):
@@ -360,7 +363,8 @@ class DDPMTrainer:
                                      xh_fixed=xh_fixed, frag_fixed=list(frag_fixed), noise_fn=noise_fn)
         dev = out_samples[0][idx].device
         with torch.no_grad():
-            r = batch_rmsd([f.to(dev) for f in fragments_nodes], out_samples[0], [x.to(dev) for x in xh_fixed], idx=idx, cap=cap)
+            r = batch_rmsd([f.to(dev) for f in fragments_nodes], out_samples[0], [x.to(dev) for x in xh_fixed], idx=idx, cap=cap,
+                           match_order=match_order)
             self.last_rmsds = r
             fin = torch.isfinite(r)
             cnt = fin.sum()
