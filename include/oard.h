@@ -586,6 +586,34 @@ int oard_matched_rmsd(const float* a_dev, int64_t lda, const float* b_dev, int64
                       float* aligned_dev /* or NULL */, int32_t* perm_dev /* or NULL */, int32_t* status_dev /* or NULL */,
                       oard_stream_t stream);
 
+/* ---- ranking metrics: midranks per segment, AUROC, Pearson, Spearman --------------------------------------------------------------
+ * Replaces: the torchmetrics objects ConfModule logs through (oa_reactdiff/trainer/pl_trainer.py:475 BinaryAUROC, :485-486
+ * PearsonCorrCoef / SpearmanCorrCoef; used at :568, :579, :581), per segment instead of per call.
+ * score_dev / target_dev: contiguous float32 [n]; segment g is rows seg_ptr[g] .. seg_ptr[g + 1] (seg_ptr_dev: n_segments + 1 ascending
+ * int32, as for oard_kabsch_rmsd); every boundary is clamped to [0, n] on the device, so a wrong seg_ptr reads nothing outside the arrays.
+ * rank_score_dev / rank_target_dev (or NULL): float64 [n], the 1-based average rank ("midrank") of every row among the rows of its
+ *     segment, rank_i = #{x_j < x_i} + (#{x_j == x_i} + 1) / 2 = scipy.stats.rankdata(method="average"); int32 compare-and-count, nothing
+ *     is sorted: exact half-integers, independent of launch shape and row order; O(sum n_g^2) compares.  Rows of no segment get NaN.
+ * out_dev (or NULL): [n_segments, OARD_RANK_COLS] float64, per segment
+ *     0 n_g   1 n_pos = rows with target >= 0.5   2 AUROC   3 Pearson(score, target)   4 Spearman = Pearson of the two midranks
+ *     5 mean |score - target|   6 mean score   7 mean target
+ *     AUROC = (R_pos - n_pos (n_pos + 1) / 2) / (n_pos n_neg), R_pos the score-midrank sum of the positive rows as an exact integer of
+ *     twice-ranks (ties count half: BinaryAUROC(thresholds=None)); Pearson from centred sums behind a first pass for the means; float64
+ *     sums in a fixed order, one wavefront per segment: a segment's bits depend on its own values alone (csrc/oard_rank.h).
+ *     Without both rank arrays the ranks behind cols 2 and 4 are counted inside that wavefront - meant for short segments; pass both
+ *     arrays for long ones.
+ * Empty segment: col 0 = 0, the rest NaN.  n_pos == 0 or n_pos == n_g: AUROC = 0 (torchmetrics' value where undefined).  Zero variance:
+ * Pearson / Spearman NaN (0 / 0, as scipy).  A NaN in score or target of a segment: its cols 2-7 and its ranks are NaN, nothing faults,
+ * the other segments are untouched.  +-inf is ordered like any value (ranks, AUROC, Spearman defined; cols 3, 5-7 follow IEEE).
+ * OARD_EINVAL - before any HIP call - for n < 0 or n >= 2^31, n_segments < 0, all three outputs NULL, and with n_segments > 0 for a null
+ * score_dev / target_dev / seg_ptr_dev; n_segments == 0 returns OARD_OK without a launch.  No oard_config, no topology, no allocation;
+ * asynchronous on `stream`, capturable. */
+#define OARD_RANK_COLS 8
+int oard_rank_metrics(const float* score_dev, const float* target_dev, int64_t n,
+                      const int32_t* seg_ptr_dev, int64_t n_segments,
+                      double* rank_score_dev /* [n] or NULL */, double* rank_target_dev /* [n] or NULL */,
+                      double* out_dev /* [n_segments, 8] or NULL */, oard_stream_t stream);
+
 /* The library's own streams of the current device(three non-blocking streams, chosen once per device so that each runs on a hardware
  * queue of its own beside the caller's stream - the runtime serves a process's streams from 4 queues): 0 = the training sweep's
  * gradient stream (and the second sub-batch of a multi-part forward), 1 = the third sub-batch, 2 = topology uploads (and the fourth).

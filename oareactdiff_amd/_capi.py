@@ -8,7 +8,7 @@ import os
 from .build import LIB
 
 OARD_MAX_OBJECTS = 8
-ABI_VERSION = 2045            # OARD_VERSION of csrc/oard_hip.hip (checked by lib(): a stale library is refused, not misread)
+ABI_VERSION = 2046            # OARD_VERSION of csrc/oard_hip.hip (checked by lib(): a stale library is refused, not misread)
 OARD_OK, OARD_EINVAL, OARD_ENOTCOMPLETE, OARD_EHIP, OARD_ENOMEM = 0, -1, -2, -3, -4
 ERRORS = {OARD_EINVAL: "invalid argument / unsupported configuration", OARD_ENOTCOMPLETE: "topology is not complete-per-sample",
           OARD_EHIP: "HIP runtime error", OARD_ENOMEM: "workspace too small"}
@@ -27,7 +27,7 @@ EXPORTS = ["oard_version", "oard_supported", "oard_param_count", "oard_packed_by
            "oard_train_scratch_bytes", "oard_train_scratch_poison", "oard_train_scratch_entry", "oard_train_tail_backward",
            "oard_train_layer_backward", "oard_train_init_backward", "oard_train_stage_backward",
            "oard_loss_prepare", "oard_loss_terms", "oard_adamw_step", "oard_adamw_step_dev", "oard_nan_replace",
-           "oard_adamw_step_ema", "oard_adamw_step_dev_ema", "oard_ema_update", "oard_kabsch_rmsd", "oard_matched_rmsd",
+           "oard_adamw_step_ema", "oard_adamw_step_dev_ema", "oard_ema_update", "oard_kabsch_rmsd", "oard_matched_rmsd", "oard_rank_metrics",
            "oard_graph_create", "oard_graph_destroy", "oard_graph_num_nodes", "oard_graph_num_edges", "oard_graph_object_rows",
            "oard_graph_is_complete", "oard_graph_workspace_bytes", "oard_graph_forward", "oard_library_stream",
            "oard_confidence_forward", "oard_confidence_forward_train", "oard_confidence_tail_backward"]
@@ -162,6 +162,7 @@ def lib() -> C.CDLL:
     L.oard_ema_update.argtypes = [vp, vp, i64, cd, vp]; L.oard_ema_update.restype = ci
     L.oard_kabsch_rmsd.argtypes = [vp, i64, vp, i64, vp, i64, ci, cf, vp, vp, vp, vp]; L.oard_kabsch_rmsd.restype = ci
     L.oard_matched_rmsd.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, ci, cf, ci, vp, vp, vp, vp, vp, vp]; L.oard_matched_rmsd.restype = ci
+    L.oard_rank_metrics.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]; L.oard_rank_metrics.restype = ci
     L.oard_library_stream.argtypes = [ci, pvp]; L.oard_library_stream.restype = ci
     # general edge lists (csrc/oard_general.hip)
     L.oard_graph_create.argtypes = [cfgp, vp, vp, i64, vp, i64, pvp]; L.oard_graph_create.restype = ci

@@ -17,7 +17,15 @@ flag, loss, logged metrics].
 
 Logged (`info`): classification `acc`, `precision`, `F1` at threshold 0.5 and `mean` (the share of predictions that round to 1);
 regression `MAE` and `mean` - torch ops on the device.  The reference also logs `AUC` (classification), `Pearson` and `Spearman`
-(regression) through torchmetrics, which this package does not depend on: they are left out.
+(regression) through torchmetrics (pl_trainer.py:568, 579, 581), which this package does not depend on: `ConfidenceTrainer(...,
+rank_metrics=True)` adds them under the reference's names from `metrics.rank_metrics` (`oard_rank_metrics`, csrc/oard_rank.h) - AUC of the
+float32 `sigmoid(preds)` the reference feeds to torchmetrics, positives `target >= 0.5`, ties counted half.  They travel in the same host
+read, which is float64 on that path.  Off by default: the logged keys and every bit of a step are then what they were without it.
+
+VALIDATION: `validation_step(batch)` is `_shared_eval` (pl_trainer.py:619-629) without a host read - an inference-mode forward on the
+live weights or on the average, the row [totloss, metrics...] on the device, predictions and targets remembered on the device -, and
+`validation_epoch_end()` is `average_over_batch_metrics` (trainer/_metrics.py:6-22) in ONE host read, plus the pooled AUC / Pearson /
+Spearman over every remembered prediction as one segment: a mean of per-batch AUCs is not the AUC of the set.
 
 Host-sync step on one device only: no `host_sync=False`, no micro-batches, no process group (out of scope).
 """
@@ -33,7 +41,8 @@ from torch import Tensor
 from . import _capi
 from .confidence import FEATURE_MAPPING, Confidence, _Layout
 from .graph_tools import get_n_frag_switch
-from .trainer import Queue
+from .metrics import rank_metrics
+from .trainer import Queue, bind_to_average
 
 DEFAULT_OPTIMIZER = dict(lr=5e-4, betas=(0.9, 0.999), weight_decay=0, amsgrad=True)       # train_confidence_ts1x.py:82-87
 CLIP_MEAN_FACTOR, CLIP_STD_FACTOR = 2.5, 3.0                                                # pl_trainer.py:649
@@ -41,15 +50,17 @@ CLIP_MEAN_FACTOR, CLIP_STD_FACTOR = 2.5, 3.0                                    
 
 class ConfidenceTrainer:
     def __init__(self, confidence: Confidence, optimizer_config: Optional[Dict] = None, clip_grad: bool = True,
-                 classification: bool = True, target_key: str = "rmsd", ema_decay: Optional[float] = None):
+                 classification: bool = True, target_key: str = "rmsd", ema_decay: Optional[float] = None, rank_metrics: bool = False):
         """`confidence`: a `Confidence(..., trainable=True)` on a ROCm device.  A batch is `(representations, res)` with
         `res["condition"]` and the targets `res[target_key]` ([B], by reaction id), as `ConfModule.compute_loss` takes it.
         `ema_decay=d`: a float32 moving average of the trained weights in `flat_ema`, updated inside the AdamW kernel after every step
-        that is taken (`oard_adamw_step_ema`; `d` is the weight of the old average, as in `DDPMTrainer`)."""
+        that is taken (`oard_adamw_step_ema`; `d` is the weight of the old average, as in `DDPMTrainer`).
+        `rank_metrics=True`: `AUC` (classification) or `Pearson` and `Spearman` (regression) join the logged metrics (module docstring)."""
         if not isinstance(confidence, Confidence) or not confidence.trainable:
             raise ValueError("ConfidenceTrainer needs a Confidence module built with trainable=True")
         self.confidence = confidence
         self.classification, self.target_key, self.clip_grad = bool(classification), target_key, bool(clip_grad)
+        self.rank_metrics = bool(rank_metrics)
         P = confidence._train_params()
         self.names: List[str] = list(P)
         self.params: List[Tensor] = list(P.values())
@@ -65,6 +76,7 @@ class ConfidenceTrainer:
         for p in self.params:
             starts.append(n)
             n = (n + p.numel() + 3) // 4 * 4
+        self._starts = starts
         self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.flat_param = torch.zeros(n, dtype=torch.float32, device=dev)
         with torch.no_grad():
@@ -84,6 +96,13 @@ class ConfidenceTrainer:
             raise ValueError(f"ema_decay must lie in [0, 1] (got {ema_decay!r})")
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.flat_ema = None if ema_decay is None else self.flat_param.detach().clone()
+        self._ema_confidence: Optional[Confidence] = None
+        # validation: rows [totloss, metrics...] of the batches seen, their predictions / targets in grow-only device buffers
+        self._val_rows: List[Tensor] = []
+        self._val_names: List[str] = []
+        self._val_pred: Optional[Tensor] = None
+        self._val_target: Optional[Tensor] = None
+        self._val_n = 0
         self.opt_config = dict(DEFAULT_OPTIMIZER, **(optimizer_config or {}))
         # what configure_optimizers returns (pl_trainer.py:488-499): its param_groups[0] is read at EVERY step, so a scheduler attached
         # to it takes effect; the moments live in the flat buffers here (state_dict)
@@ -124,8 +143,18 @@ class ConfidenceTrainer:
     def _targets(self, res, dev) -> Tensor:
         return res[self.target_key].detach().to(device=dev, dtype=torch.float32).reshape(-1)
 
-    def _loss_and_metrics(self, logits: Tensor, y: Tensor) -> Tuple[Tensor, List[str], Tensor]:
-        """-> (loss, metric names, metric values [len(names)]) on the device; pl_trainer.py:564-584."""
+    def _ranked(self, names: List[str], vals: Tensor, pred: Tensor, y: Tensor) -> Tuple[List[str], Tensor]:
+        """The logged metrics with the ranking ones behind them (`rank_metrics=True`): one kernel call on the batch as one segment."""
+        if not self.rank_metrics:
+            return names, vals
+        m = rank_metrics(pred, y)
+        if self.classification:
+            return names + ["AUC"], torch.cat([vals.double(), m.auroc])
+        return names + ["Pearson", "Spearman"], torch.cat([vals.double(), m.pearson, m.spearman])
+
+    def _loss_and_metrics(self, logits: Tensor, y: Tensor) -> Tuple[Tensor, List[str], Tensor, Tensor]:
+        """-> (loss, metric names, metric values [len(names)], the predictions they are computed on: sigmoid(preds) or preds) on the
+        device; pl_trainer.py:564-584.  The values are float32, or float64 with `rank_metrics`."""
         x = logits.reshape(-1)
         if self.classification:
             p = torch.sigmoid(x)
@@ -138,16 +167,19 @@ class ConfidenceTrainer:
             zero = torch.zeros((), device=x.device)
             prec = torch.where(tp + fp > 0, tp / (tp + fp).clamp(min=1), zero)              # torchmetrics: 0 where undefined
             f1 = torch.where(2 * tp + fp + fn > 0, 2 * tp / (2 * tp + fp + fn).clamp(min=1), zero)
-            return loss, ["acc", "precision", "F1", "mean"], torch.stack([(hit == pos).float().mean(), prec, f1, p.round().mean()])
+            names, vals = self._ranked(["acc", "precision", "F1", "mean"],
+                                       torch.stack([(hit == pos).float().mean(), prec, f1, p.round().mean()]), p, y)
+            return loss, names, vals, p
         loss = torch.nn.functional.mse_loss(x, y)
-        return loss, ["MAE", "mean"], torch.stack([(x - y).abs().mean(), x.mean()])
+        names, vals = self._ranked(["MAE", "mean"], torch.stack([(x - y).abs().mean(), x.mean()]), x, y)
+        return loss, names, vals, x
 
     def compute_loss(self, batch) -> Tuple[Tensor, Dict[str, float]]:
         """`ConfModule.compute_loss` (pl_trainer.py:554-585) -> (loss, info).  Under autograd the loss carries the module's
         `ConfidenceFunction`; the logged metrics cost one host read."""
         representations, res = batch
         logits = self.confidence.forward(representations, res["condition"])
-        loss, names, vals = self._loss_and_metrics(logits, self._targets(res, logits.device))
+        loss, names, vals, _ = self._loss_and_metrics(logits, self._targets(res, logits.device))
         return loss, dict(zip(names, vals.detach().tolist()))
 
     # ---- the step -------------------------------------------------------------------------------------------------------------------
@@ -175,7 +207,7 @@ class ConfidenceTrainer:
             y = self._targets(res, dev)
             if y.numel() != logits.numel():
                 raise _capi.OardError(f"{y.numel()} targets for {logits.numel()} reactions")
-            loss, names, vals = self._loss_and_metrics(logits, y)
+            loss, names, vals, _ = self._loss_and_metrics(logits, y)
             B = logits.numel()
             dlogits = (torch.sigmoid(logits) - y) / B if self.classification else 2.0 * (logits - y) / B
             conf.backward_sweep(state, dlogits, self._dests, stream)
@@ -194,6 +226,8 @@ class ConfidenceTrainer:
         with torch.cuda.device(dev):
             _capi.check(getattr(_capi.lib(), entry)(*args, torch.cuda.current_stream(dev).cuda_stream), entry)
         self.confidence.invalidate_packed()              # the weights changed behind torch's version counters
+        if self._ema_confidence is not None:
+            self._ema_confidence.invalidate_packed()
 
     def training_step(self, batch) -> Dict[str, float]:
         """One step; -> info: `loss`, `skipped`, the logged metrics of `compute_loss`, and with clipping `grad_norm` / `max_grad_norm`.
@@ -207,7 +241,10 @@ class ConfidenceTrainer:
         bad = (~torch.isfinite(norm + loss)).to(torch.float32)
         if conf.nan_seen is not None:
             bad = bad + (conf.nan_seen[0] != 0).to(torch.float32)
-        stats = torch.cat([norm.reshape(1), bad.reshape(1), loss.reshape(1), vals]).tolist()          # the one host sync
+        head = [norm.reshape(1), bad.reshape(1), loss.reshape(1)]
+        if self.rank_metrics:                                  # the ranking metrics are float64: widen the rest, which is exact
+            head = [h.double() for h in head]
+        stats = torch.cat(head + [vals]).tolist()              # the one host sync
         grad_norm, flag = stats[0], stats[1]
         info: Dict[str, float] = dict(zip(names, stats[3:]))
         skipped = flag != 0 or not math.isfinite(grad_norm)
@@ -233,3 +270,81 @@ class ConfidenceTrainer:
         info["skipped"] = int(skipped)
         return info
 
+    # ---- validation -----------------------------------------------------------------------------------------------------------------
+    @property
+    def ema_confidence(self) -> Confidence:
+        """A second, frozen `Confidence` of the live one's configuration whose trained tensors are VIEWS into `flat_ema` (every other
+        tensor shares storage with the live module's), as `DDPMTrainer.ema_dynamics`: built at the first look, with packed weights
+        and call buffers of its own, so a call on the average touches neither the live weights nor their packed blob; every taken step
+        marks its packed weights stale."""
+        if self._ema_confidence is None:
+            if self.flat_ema is None:
+                raise ValueError("this trainer keeps no average of the weights (ConfidenceTrainer(ema_decay=...))")
+            live = self.confidence
+            args = dict(live._ctor_args, model_config=dict(live._ctor_args["model_config"]), device=torch.device("meta"))
+            for k in ("update_pocket_coords", "condition_time"):          # fixed by Confidence itself
+                args.pop(k, None)
+            shadow = Confidence(**args)
+            shadow.device = live.device
+            where = {id(p): off for p, off in zip(self.params, self._starts)}
+            shadow._ordered_tensors()                      # resolves the (owning module, attribute) pair of every state-dict entry
+            bind_to_average(shadow._slots[1] + shadow._readout_slot_list(),
+                            live._ordered_tensors() + live._readout_tensors(self.flat_ema.device), self.flat_ema, where)
+            shadow.edge_precision, shadow.train_edge_precision = live.edge_precision, live.train_edge_precision
+            shadow.eval()
+            self._ema_confidence = shadow
+        return self._ema_confidence
+
+    def _remember(self, pred: Tensor, y: Tensor) -> None:
+        n, B = self._val_n, int(pred.numel())
+        if self._val_pred is None or self._val_pred.numel() < n + B:
+            cap = max(2 * (n + B), 1024)
+            grown = [torch.empty(cap, dtype=torch.float32, device=pred.device) for _ in range(2)]
+            if n:
+                grown[0][:n].copy_(self._val_pred[:n])
+                grown[1][:n].copy_(self._val_target[:n])
+            self._val_pred, self._val_target = grown
+        self._val_pred[n: n + B].copy_(pred)
+        self._val_target[n: n + B].copy_(y)
+        self._val_n = n + B
+
+    @torch.no_grad()
+    def validation_step(self, batch, weights: str = "live") -> Tensor:
+        """`ConfModule.validation_step` (`_shared_eval`, pl_trainer.py:619-629) without a host read: an inference-mode forward - no tape,
+        no gradient work - on the live weights, or with `weights="ema"` on the average (`ema_confidence`; ValueError for a trainer
+        without `ema_decay`), which leaves the live weights and their packed blob alone.  -> the device row [totloss, metrics...] in the
+        order of `compute_loss`'s `info` (float64 with `rank_metrics`).  The batch's predictions (sigmoid(preds) or preds) and targets
+        are appended to device buffers that only grow, for `validation_epoch_end`."""
+        if weights not in ("live", "ema"):
+            raise ValueError(f"weights must be 'live' or 'ema' (got {weights!r})")
+        conf = self.confidence if weights == "live" else self.ema_confidence
+        representations, res = batch
+        logits = conf.forward(representations, res["condition"]).reshape(-1)
+        y = self._targets(res, logits.device)
+        if y.numel() != logits.numel():
+            raise _capi.OardError(f"{y.numel()} targets for {logits.numel()} reactions")
+        loss, names, vals, pred = self._loss_and_metrics(logits, y)
+        row = torch.cat([loss.reshape(1).to(vals.dtype), vals])
+        self._remember(pred, y)
+        self._val_rows.append(row)
+        self._val_names = ["totloss"] + names
+        return row
+
+    def validation_epoch_end(self) -> Dict[str, float]:
+        """`ConfModule.validation_epoch_end` (pl_trainer.py:634-640) over the `validation_step` calls since the last one, in ONE host
+        read: `val-<k>` for `totloss` and every logged metric, the mean over the batches that gave a number (`nanmean`).  The reference's
+        `average_over_batch_metrics` (trainer/_metrics.py:6-22) skips NaN batches too - except the first, whose NaN poisons its mean;
+        that quirk is not reproduced.  And what a ranking model is judged by: `val-pooled-AUC` (classification) or `val-pooled-Pearson`
+        and `val-pooled-Spearman` (regression) over ALL remembered predictions as one segment - not a mean of per-batch numbers.
+        Forgets the batches (the buffers stay allocated).  No `validation_step` since the last call: an empty dict."""
+        if not self._val_rows:
+            return {}
+        names = self._val_names
+        means = torch.nanmean(torch.stack(self._val_rows).double(), dim=0)
+        m = rank_metrics(self._val_pred[:self._val_n], self._val_target[:self._val_n])
+        pooled = {"AUC": m.auroc} if self.classification else {"Pearson": m.pearson, "Spearman": m.spearman}
+        stats = torch.cat([means] + list(pooled.values())).tolist()          # the one host read
+        out = {f"val-{k}": v for k, v in zip(names, stats)}
+        out.update({f"val-pooled-{k}": v for k, v in zip(pooled, stats[len(names):])})
+        self._val_rows, self._val_n = [], 0
+        return out

@@ -23,7 +23,7 @@ as a frozen one.  `conf_trainer.ConfidenceTrainer` is the reference's `ConfModul
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -58,6 +58,35 @@ def rank_candidates(scores: Tensor, n_reactions: int) -> Tuple[Tensor, Tensor]:
     per_reaction = scores.reshape(-1, n_reactions).t()
     order = torch.argsort(per_reaction, dim=1, descending=True, stable=True)
     return order[:, 0], order
+
+
+class RankingReport(NamedTuple):
+    """Per reaction, `[n_reactions]` device tensors (`ranking_report`)."""
+    spearman: Tensor          # float64: rank correlation of the scores with -RMSD over the K candidates (NaN where either is constant)
+    top1_rmsd: Tensor         # RMSD of the candidate `rank_candidates` picks
+    best_rmsd: Tensor         # the smallest RMSD among the candidates
+    hit_at_1: Tensor          # bool: top1_rmsd < threshold
+    regret: Tensor            # top1_rmsd - best_rmsd
+
+
+def ranking_report(scores: Tensor, rmsd: Tensor, n_reactions: int, threshold: float = 0.2) -> RankingReport:
+    """How good was the ordering `rank_candidates` gives, against known RMSDs?  `scores`, `rmsd`: [K * n_reactions], candidate-major
+    as for `rank_candidates` -> `RankingReport`.  The Spearman correlation is one `oard_rank_metrics` call with one segment of K
+    candidates per reaction (ties in the scores get their average rank); a higher score should mean a lower RMSD, hence -RMSD.
+    Device tensors in, device tensors out, no host read."""
+    from .metrics import rank_metrics
+    scores, rmsd = scores.reshape(-1), rmsd.reshape(-1)
+    if rmsd.numel() != scores.numel():
+        raise ValueError(f"{scores.numel()} scores for {rmsd.numel()} RMSDs")
+    best_index, _ = rank_candidates(scores, n_reactions)
+    K = scores.numel() // n_reactions
+    s_rm = scores.reshape(K, n_reactions).t().contiguous()                 # reaction-major: a reaction's candidates are one segment
+    r_rm = rmsd.reshape(K, n_reactions).t().contiguous()
+    sizes = torch.full((n_reactions,), K, dtype=torch.int64, device=scores.device)
+    spearman = rank_metrics(s_rm, -r_rm, sizes).spearman
+    top1 = r_rm.gather(1, best_index.reshape(-1, 1)).reshape(-1)
+    best = r_rm.min(dim=1).values
+    return RankingReport(spearman, top1, best, top1 < threshold, top1 - best)
 
 
 class ConfidenceFunction(torch.autograd.Function):
@@ -132,7 +161,8 @@ class Confidence(EGNNDynamics):
         self._t0: Optional[Tensor] = None
 
     # ------------------------------------------------------------------------------------------
-    def _readout_tensors(self, dev) -> List[Tensor]:
+    def _readout_slot_list(self) -> list:
+        """The (owning module, attribute) pair of every readout tensor, in READOUT_NAMES order (resolved once)."""
         if self._readout_slots is None:
             slots = []
             for name in READOUT_NAMES:
@@ -141,7 +171,10 @@ class Confidence(EGNNDynamics):
                     mod = mod[int(p)] if p.isdigit() and isinstance(mod, torch.nn.ModuleList) else getattr(mod, p)
                 slots.append((mod, name.rsplit(".", 1)[1]))
             self._readout_slots = slots
-        out = [mod._parameters[attr] for mod, attr in self._readout_slots]
+        return self._readout_slots
+
+    def _readout_tensors(self, dev) -> List[Tensor]:
+        out = [mod._parameters[attr] for mod, attr in self._readout_slot_list()]
         for t in out:
             if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
                 raise _capi.OardError("the readout parameters must be contiguous float32 tensors on the call's device")
@@ -314,3 +347,4 @@ class Confidence(EGNNDynamics):
         return torch.sigmoid(logits) if probability else logits
 
     rank_candidates = staticmethod(rank_candidates)
+    ranking_report = staticmethod(ranking_report)

@@ -29,7 +29,7 @@
 #include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
-#define OARD_VERSION 2045      // + oard_matched_rmsd (2044: oard_confidence_forward_train, oard_confidence_tail_backward; 2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
+#define OARD_VERSION 2046      // + oard_rank_metrics (2045: oard_matched_rmsd; 2044: oard_confidence_forward_train, oard_confidence_tail_backward; 2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
 // The first-generation kernels (weights straight from L2, one wave per 16 nodes: gcl_variant / equi_variant / node_variant 0) are the
 // A/B baseline of round 1 and a cross-check in tests/test_hip_parity.py::test_every_kernel_variant_is_parity_green; they are compiled
 // into experiment builds (-DOARD_EXPERIMENTS) only - a product library refuses those variants (oard_debug_option returns OARD_EINVAL).
@@ -2217,6 +2217,7 @@ int oard_wgrad(const float* dY, int ldY, int ncY, int o_len, int o_pad, int MO, 
 #include "oard_loss.h"
 #include "oard_kabsch.h"     // k_kabsch_rmsd: the validation metric (oard_kabsch_rmsd)
 #include "oard_match.h"      // k_matched_rmsd: the same with the atoms matched first (oard_matched_rmsd)
+#include "oard_rank.h"       // k_rank_count, k_rank_stats: midranks per segment, AUROC / Pearson / Spearman (oard_rank_metrics)
 extern "C" {
 
 // ---- the backward sweep through the C ABI (include/oard.h) ------------------------------------------------------------------------
@@ -2514,6 +2515,25 @@ int oard_matched_rmsd(const float* a, int64_t lda, const float* b, int64_t ldb, 
     LAUNCH(F_OTHER, k_matched_rmsd, n_segments, 64, (hipStream_t)stream, a, (long long)lda, b, (long long)ldb, species_a, species_b, seg_ptr,
            flags, cap, exact_limit, rmsd, rot, aligned, perm, status);
     HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+// ---- midranks per segment and the ranking metrics on them (pl_trainer.py:475,485-486,568,579,581; oard_rank.h) --------------------------------
+int oard_rank_metrics(const float* score, const float* target, int64_t n, const int32_t* seg_ptr, int64_t n_segments, double* rank_score,
+                      double* rank_target, double* out, oard_stream_t stream) {
+    if (n < 0 || n > 0x7fffffffLL || n_segments < 0 || n_segments >= 0x7fffffffLL || (!rank_score && !rank_target && !out)) return OARD_EINVAL;
+    if (n_segments > 0 && (!score || !target || !seg_ptr)) return OARD_EINVAL;
+    if (n_segments == 0) return OARD_OK;
+    if ((rank_score || rank_target) && n > 0) {
+        LAUNCH(F_OTHER, k_rank_count, cdiv(n, RANK_ROWS), RANK_BLOCK, (hipStream_t)stream, score, target, (int)n, seg_ptr, (int)n_segments,
+               rank_score, rank_target);
+        HIP_TRY(hipGetLastError());
+    }
+    if (out) {
+        LAUNCH(F_OTHER, k_rank_stats, n_segments, 64, (hipStream_t)stream, score, target, (int)n, seg_ptr, (const double*)rank_score,
+               (const double*)rank_target, out);
+        HIP_TRY(hipGetLastError());
+    }
     return OARD_OK;
 }
 

@@ -17,10 +17,16 @@ transition state keeps the atom order of the fixed reactant and product, so it i
 STILL DIFFERENT from the reference: pymatgen's genetic matcher with its `threshold`, and the axis heuristics of its Hungarian matcher,
 have no counterpart - they define no function of the inputs.
 
+RANKING METRICS (`oard_rank_metrics`, csrc/oard_rank.h): `rank_metrics(score, target, sizes)` gives per segment what the reference's
+`ConfModule` logs through torchmetrics - `BinaryAUROC`, `PearsonCorrCoef`, `SpearmanCorrCoef` (trainer/pl_trainer.py:475, 485-486) -, and
+`midrank` the average ranks with ties they rest on (`scipy.stats.rankdata(method="average")`).  Integer compare-and-count instead of a
+sort, float64 sums in a fixed order: ties are exact, ragged segments are one launch, a segment's bits depend on its own values alone, and
+nothing is read back.  `binary_auroc`, `pearson_corrcoef` and `spearman_corrcoef` select one column.
+
 No CPU fallback: tensors that are not on a ROCm device raise `OardError`, as everywhere else in the package."""
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Union
+from typing import List, NamedTuple, Optional, Sequence, Union
 
 import torch
 from torch import Tensor
@@ -178,3 +184,92 @@ def batch_rmsd(fragments_nodes: List[Tensor], out_samples: List[Tensor], xh: Lis
         return kabsch_rmsd(xh[idx], out_samples[idx], fragments_nodes[idx], ignore_chirality=ignore_chirality, cap=cap)
     return matched_rmsd(xh[idx], out_samples[idx], fragments_nodes[idx], xh[idx][:, -1], out_samples[idx][:, -1],
                         ignore_chirality=ignore_chirality, cap=cap)
+
+
+# ---- ranking metrics (csrc/oard_rank.h) --------------------------------------------------------------------------------------------------
+RANK_COLS = 8                 # OARD_RANK_COLS of include/oard.h
+
+
+class RankMetrics(NamedTuple):
+    """Per segment, `[G]` float64 device tensors (the columns of `oard_rank_metrics`)."""
+    n: Tensor
+    n_pos: Tensor
+    auroc: Tensor
+    pearson: Tensor
+    spearman: Tensor
+    mae: Tensor
+    mean_score: Tensor
+    mean_target: Tensor
+
+
+def _values(x: Tensor, name: str) -> Tensor:
+    """A contiguous float32 `[n]` device tensor, passed through as it is; anything else is converted, which copies (as `_coords`)."""
+    if not isinstance(x, Tensor):
+        raise ValueError(f"{name} must be a tensor (got {type(x).__name__})")
+    if not x.is_cuda:
+        raise _capi.OardError(f"the ranking metrics need {name} on a ROCm device (there is no CPU fallback)")
+    x = x.detach().reshape(-1)
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    return x.contiguous()
+
+
+def _rank_call(score: Tensor, target: Tensor, sizes, want_out: bool):
+    """One `oard_rank_metrics` call -> (ranks [2, n] float64: of score, of target; out [G, 8] | None).  Both rank arrays are always
+    handed over: the launch-wide counting kernel then serves the columns that need ranks, whatever the segment lengths."""
+    score, target = _values(score, "score"), _values(target, "target")
+    dev = score.device
+    if target.device != dev:
+        raise ValueError("score and target live on different devices")
+    n = int(score.numel())
+    if int(target.numel()) != n:
+        raise ValueError(f"score has {n} entries, target has {int(target.numel())}")
+    if sizes is None:                                # one segment of everything: [0, n] in one launch, nothing copied from the host
+        seg_ptr = torch.arange(0, n + 1, n, dtype=torch.int32, device=dev) if n else torch.zeros(2, dtype=torch.int32, device=dev)
+        G = 1
+    else:
+        seg_ptr, G = _segments(sizes, n, dev)
+    # with a segment the kernel writes every rank (NaN for the rows of no segment); without one nothing is launched
+    ranks = torch.empty(2, n, dtype=torch.float64, device=dev) if G else torch.full((2, n), float("nan"), dtype=torch.float64, device=dev)
+    out = torch.empty(G, RANK_COLS, dtype=torch.float64, device=dev) if want_out else None
+    if G and (n or want_out):
+        if n == 0:                                   # an empty tensor has no address; the kernels read nothing
+            score = target = torch.zeros(1, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _capi.lib().oard_rank_metrics(score.data_ptr(), target.data_ptr(), n, seg_ptr.data_ptr(), G,
+                                               ranks[0].data_ptr() if n else None, ranks[1].data_ptr() if n else None,
+                                               None if out is None else out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _capi.check(rc, "oard_rank_metrics")
+    return ranks, out
+
+
+def midrank(x: Tensor, sizes: Union[Tensor, Sequence[int], None] = None) -> Tensor:
+    """1-based average ranks of `x` inside every segment (segment g: the next `sizes[g]` entries; None: one segment of everything) ->
+    `[n]` float64 device tensor, exact half-integers: `scipy.stats.rankdata(method="average")` per segment.  Entries of no segment, and
+    every entry of a segment that holds a NaN, are NaN.  `sizes` as for `kabsch_rmsd` (a device tensor is never read back)."""
+    return _rank_call(x, x, sizes, False)[0][0]
+
+
+def rank_metrics(score: Tensor, target: Tensor, sizes: Union[Tensor, Sequence[int], None] = None) -> RankMetrics:
+    """Per segment of `score` and `target` (`[n]` each; `sizes=None`: one segment of everything): the number of entries, the number of
+    positives (`target >= 0.5`), AUROC of `score` for those positives (ties count half, `BinaryAUROC(thresholds=None)`), Pearson and
+    Spearman correlation, mean |score - target| and the two means -> `RankMetrics` of `[G]` float64 device tensors, no host read.
+    An empty segment: n = 0, the rest NaN.  One class only: AUROC 0.  A constant argument: Pearson / Spearman NaN.  A NaN in a segment:
+    everything but n and n_pos NaN there, the other segments untouched.  Inputs that are not contiguous float32 are converted."""
+    out = _rank_call(score, target, sizes, True)[1]
+    return RankMetrics(*out.unbind(1))
+
+
+def binary_auroc(pred: Tensor, target: Tensor, sizes: Union[Tensor, Sequence[int], None] = None) -> Tensor:
+    """`rank_metrics(...).auroc`: torchmetrics' `BinaryAUROC(thresholds=None)` (pl_trainer.py:475) per segment, positives `target >= 0.5`."""
+    return rank_metrics(pred, target, sizes).auroc
+
+
+def pearson_corrcoef(pred: Tensor, target: Tensor, sizes: Union[Tensor, Sequence[int], None] = None) -> Tensor:
+    """`rank_metrics(...).pearson`: torchmetrics' `PearsonCorrCoef` (pl_trainer.py:485) per segment."""
+    return rank_metrics(pred, target, sizes).pearson
+
+
+def spearman_corrcoef(pred: Tensor, target: Tensor, sizes: Union[Tensor, Sequence[int], None] = None) -> Tensor:
+    """`rank_metrics(...).spearman`: torchmetrics' `SpearmanCorrCoef` (pl_trainer.py:486) per segment."""
+    return rank_metrics(pred, target, sizes).spearman

@@ -42,6 +42,24 @@ UNUSED_PREFIXES = ("model.distance_embedding.", "model.last_layer.")
 DEFAULT_OPTIMIZER = dict(lr=2.5e-4, betas=(0.9, 0.999), weight_decay=0, amsgrad=True)      # train_ts1x.py:66-71
 
 
+def bind_to_average(slots, tensors, flat_ema: Tensor, where: Dict[int, int]) -> None:
+    """Fills a shadow module (`DDPMTrainer.ema_dynamics`, `ConfidenceTrainer.ema_confidence`): slot k, an (owning module, attribute)
+    pair of the shadow, receives the live module's `tensors[k]` - as a VIEW into `flat_ema` at offset `where[id(tensor)]` if it is a
+    trained tensor, else the live tensor itself (shared storage).  A tensor that sits in several slots stays one object;
+    requires_grad is False throughout."""
+    made: Dict[int, Tensor] = {}
+    for (mod, attr), t in zip(slots, tensors):
+        new = made.get(id(t))
+        if new is None:
+            o = where.get(id(t))
+            data = t.detach() if o is None else flat_ema[o: o + t.numel()].view_as(t)
+            new = made[id(t)] = nn.Parameter(data, requires_grad=False) if isinstance(t, nn.Parameter) else data
+        if attr in mod._parameters:
+            mod._parameters[attr] = new
+        else:
+            mod._buffers[attr] = new
+
+
 class Queue:
     """oa_reactdiff/utils/training_tools.py:6-23."""
 
@@ -475,18 +493,8 @@ class DDPMTrainer:
             for p in self.params:
                 where[id(p)] = off
                 off += p.numel()
-            made: Dict[int, Tensor] = {}
             shadow._ordered_tensors()                  # resolves the (owning module, attribute) pair of every state-dict entry
-            for (mod, attr), t in zip(shadow._slots[1], live._ordered_tensors()):
-                new = made.get(id(t))
-                if new is None:
-                    o = where.get(id(t))
-                    data = t.detach() if o is None else ema[o: o + t.numel()].view_as(t)
-                    new = made[id(t)] = nn.Parameter(data, requires_grad=False) if isinstance(t, nn.Parameter) else data
-                if attr in mod._parameters:
-                    mod._parameters[attr] = new
-                else:
-                    mod._buffers[attr] = new
+            bind_to_average(shadow._slots[1], live._ordered_tensors(), ema, where)
             shadow.edge_precision, shadow.train_edge_precision = live.edge_precision, live.train_edge_precision
             shadow.nan_check, shadow.edge_list_path = live.nan_check, live.edge_list_path
             shadow.eval()
