@@ -42,13 +42,15 @@ from . import _capi
 from .confidence import FEATURE_MAPPING, Confidence, _Layout
 from .graph_tools import get_n_frag_switch
 from .metrics import rank_metrics
-from .trainer import Queue, bind_to_average
+from .flat_state import FlatTrainerState, bind_to_average, clip_decision
 
 DEFAULT_OPTIMIZER = dict(lr=5e-4, betas=(0.9, 0.999), weight_decay=0, amsgrad=True)       # train_confidence_ts1x.py:82-87
 CLIP_MEAN_FACTOR, CLIP_STD_FACTOR = 2.5, 3.0                                                # pl_trainer.py:649
 
 
-class ConfidenceTrainer:
+class ConfidenceTrainer(FlatTrainerState):
+    SKIP_MESSAGE = "Warning: non-finite loss / gradient / network output: step skipped ({} so far)"
+
     def __init__(self, confidence: Confidence, optimizer_config: Optional[Dict] = None, clip_grad: bool = True,
                  classification: bool = True, target_key: str = "rmsd", ema_decay: Optional[float] = None, rank_metrics: bool = False):
         """`confidence`: a `Confidence(..., trainable=True)` on a ROCm device.  A batch is `(representations, res)` with
@@ -59,7 +61,7 @@ class ConfidenceTrainer:
         if not isinstance(confidence, Confidence) or not confidence.trainable:
             raise ValueError("ConfidenceTrainer needs a Confidence module built with trainable=True")
         self.confidence = confidence
-        self.classification, self.target_key, self.clip_grad = bool(classification), target_key, bool(clip_grad)
+        self.classification, self.target_key = bool(classification), target_key
         self.rank_metrics = bool(rank_metrics)
         P = confidence._train_params()
         self.names: List[str] = list(P)
@@ -72,30 +74,11 @@ class ConfidenceTrainer:
         # tensors the forward never uses (confidence.CONF_UNUSED_PREFIXES) stay outside: no gradient, no weight decay, no step.
         # Every view starts on a 16-byte boundary - the readout kernels read the weight rows four floats at a time -; the up to three
         # floats in front of it are zero in every buffer and stay zero (AdamW of a zero weight under a zero gradient)
-        starts, n = [], 0
-        for p in self.params:
-            starts.append(n)
-            n = (n + p.numel() + 3) // 4 * 4
-        self._starts = starts
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.flat_param = torch.zeros(n, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for p, off in zip(self.params, starts):
-                end = off + p.numel()
-                self.flat_param[off:end].copy_(p.reshape(-1))
-                p.data = self.flat_param[off:end].view_as(p)
-                p.grad = self.flat_grad[off:end].view_as(p)
+        self._lay_out(4, ema_decay, bool(clip_grad))
+        n = self.layout.size
+        self._bind(torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev))
         confidence.grad_inplace = True                         # compute_loss(...)[0].backward() lands in the bucket as well
         self._dests = {id(p): p.grad for p in self.params}
-        self.exp_avg = torch.zeros_like(self.flat_param)
-        self.exp_avg_sq = torch.zeros_like(self.flat_param)
-        self.max_exp_avg_sq = torch.zeros_like(self.flat_param)
-        self.opt_step = 0
-        self.skipped_steps = 0
-        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
-            raise ValueError(f"ema_decay must lie in [0, 1] (got {ema_decay!r})")
-        self.ema_decay = None if ema_decay is None else float(ema_decay)
-        self.flat_ema = None if ema_decay is None else self.flat_param.detach().clone()
         self._ema_confidence: Optional[Confidence] = None
         # validation: rows [totloss, metrics...] of the batches seen, their predictions / targets in grow-only device buffers
         self._val_rows: List[Tensor] = []
@@ -107,37 +90,8 @@ class ConfidenceTrainer:
         # what configure_optimizers returns (pl_trainer.py:488-499): its param_groups[0] is read at EVERY step, so a scheduler attached
         # to it takes effect; the moments live in the flat buffers here (state_dict)
         self.optimizer = torch.optim.AdamW(self.params, **self.opt_config)
-        if self.clip_grad:                                     # pl_trainer.py:465-468
-            self.gradnorm_queue = Queue()
-            self.gradnorm_queue.add(3000)
 
-    # ---- resume ---------------------------------------------------------------------------------------------------------------------
-    def state_dict(self) -> Dict:
-        """What a bit-identical continuation needs besides the module's own state_dict(): the flat AdamW moments, the step counter, the
-        optimiser's hyper-parameters, the clipping history, the skipped-step counter (and the average, if one is kept)."""
-        sd: Dict = {"names": list(self.names), "skipped_steps": int(self.skipped_steps), "opt_step": int(self.opt_step),
-                    "gradnorm_queue": list(self.gradnorm_queue.items) if self.clip_grad else None,
-                    "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.optimizer.param_groups]}
-        for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"):
-            sd[k] = getattr(self, k).detach().clone()
-        if self.flat_ema is not None:
-            sd["ema_decay"], sd["ema"] = float(self.ema_decay), self.flat_ema.detach().clone()
-        return sd
-
-    def load_state_dict(self, sd: Dict) -> None:
-        if list(sd["names"]) != list(self.names):
-            raise ValueError("trainer state belongs to a different parameter list")
-        self.skipped_steps, self.opt_step = int(sd["skipped_steps"]), int(sd["opt_step"])
-        if self.clip_grad and sd.get("gradnorm_queue") is not None:
-            self.gradnorm_queue.items = [float(x) for x in sd["gradnorm_queue"]]
-        for g, saved in zip(self.optimizer.param_groups, sd["param_groups"]):
-            g.update(saved)
-        with torch.no_grad():
-            for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"):
-                getattr(self, k).copy_(sd[k].to(self.flat_param.device))
-            if self.flat_ema is not None and sd.get("ema") is not None:
-                self.ema_decay = float(sd.get("ema_decay", self.ema_decay))
-                self.flat_ema.copy_(sd["ema"].to(self.flat_ema.device))
+    # ---- resume: `state_dict()` / `load_state_dict()` are FlatTrainerState's ----------------------------------------------------------
 
     # ---- loss -----------------------------------------------------------------------------------------------------------------------
     def _targets(self, res, dev) -> Tensor:
@@ -213,21 +167,8 @@ class ConfidenceTrainer:
             conf.backward_sweep(state, dlogits, self._dests, stream)
         return loss, names, vals
 
-    def _adamw(self, gscale: float) -> None:
-        o = self.optimizer.param_groups[0]
-        dev = self.flat_grad.device
-        args = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(), float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]),
-                float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), self.opt_step, 1 if o.get("amsgrad", False) else 0,
-                float(gscale))
-        entry = "oard_adamw_step"
-        if self.flat_ema is not None:
-            entry, args = entry + "_ema", args + (self.flat_ema.data_ptr(), self.ema_decay)
-        with torch.cuda.device(dev):
-            _capi.check(getattr(_capi.lib(), entry)(*args, torch.cuda.current_stream(dev).cuda_stream), entry)
-        self.confidence.invalidate_packed()              # the weights changed behind torch's version counters
-        if self._ema_confidence is not None:
-            self._ema_confidence.invalidate_packed()
+    def _weight_readers(self):
+        return self.confidence, self._ema_confidence
 
     def training_step(self, batch) -> Dict[str, float]:
         """One step; -> info: `loss`, `skipped`, the logged metrics of `compute_loss`, and with clipping `grad_norm` / `max_grad_norm`.
@@ -249,23 +190,14 @@ class ConfidenceTrainer:
         info: Dict[str, float] = dict(zip(names, stats[3:]))
         skipped = flag != 0 or not math.isfinite(grad_norm)
         if skipped:
-            self.skipped_steps += 1
-            print(f"Warning: non-finite loss / gradient / network output: step skipped ({self.skipped_steps} so far)")
-            if self.clip_grad:
-                info["grad_norm"], info["max_grad_norm"] = grad_norm, float("nan")
+            self._count_skip(info, grad_norm)
         else:
             gscale = 1.0
             if self.clip_grad:                                 # pl_trainer.py:642-669, the factor folded into the optimiser kernel
-                max_norm = CLIP_MEAN_FACTOR * self.gradnorm_queue.mean() + CLIP_STD_FACTOR * self.gradnorm_queue.std()
-                if grad_norm > max_norm:
-                    gscale = max_norm / (grad_norm + 1e-6)
-                    self.gradnorm_queue.add(float(max_norm))
-                    print(f"Clipped gradient with value {grad_norm:.1f} while allowed {max_norm:.1f}")
-                else:
-                    self.gradnorm_queue.add(grad_norm)
+                gscale, max_norm = clip_decision(self.gradnorm_queue, grad_norm, CLIP_MEAN_FACTOR, CLIP_STD_FACTOR)
                 info["grad_norm"], info["max_grad_norm"] = grad_norm, max_norm
             self.opt_step += 1
-            self._adamw(gscale)
+            self._adamw("oard_adamw_step", (self.opt_step,), (float(gscale),))
         info["loss"] = stats[2]
         info["skipped"] = int(skipped)
         return info
@@ -286,10 +218,9 @@ class ConfidenceTrainer:
                 args.pop(k, None)
             shadow = Confidence(**args)
             shadow.device = live.device
-            where = {id(p): off for p, off in zip(self.params, self._starts)}
             shadow._ordered_tensors()                      # resolves the (owning module, attribute) pair of every state-dict entry
             bind_to_average(shadow._slots[1] + shadow._readout_slot_list(),
-                            live._ordered_tensors() + live._readout_tensors(self.flat_ema.device), self.flat_ema, where)
+                            live._ordered_tensors() + live._readout_tensors(self.flat_ema.device), self.flat_ema, self.layout.offsets())
             shadow.edge_precision, shadow.train_edge_precision = live.edge_precision, live.train_edge_precision
             shadow.eval()
             self._ema_confidence = shadow

@@ -103,24 +103,14 @@ class ConfidenceFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
+        from . import training
         conf, st = ctx.conf, ctx.state
         dev = st.xh[0].device
         P = conf._train_params()
         if conf.grad_inplace:
-            for n, p in P.items():
-                if p.grad is None:
-                    p.grad = torch.zeros_like(p)
-                if p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
-                    raise _capi.OardError(f"grad_inplace needs contiguous float32 .grad tensors ({n})")
-            dests = {id(p): p.grad for p in P.values()}
-            out = {}
+            out, dests = {}, training.inplace_gradients(P)
         else:
-            flat = torch.zeros(sum(p.numel() for p in P.values()), dtype=torch.float32, device=dev)
-            out, off = {}, 0
-            for n, p in P.items():
-                out[n] = flat[off: off + p.numel()].view_as(p)
-                off += p.numel()
-            dests = {id(p): out[n] for n, p in P.items()}
+            out, dests = training.fresh_gradients(P, dev)
         with torch.cuda.device(dev), torch.no_grad():
             conf.backward_sweep(st, dlogits, dests, torch.cuda.current_stream(dev).cuda_stream)
         ctx.state = None

@@ -36,50 +36,11 @@ from torch import Tensor, nn
 
 from . import _capi, training
 from .dynamics import _CallBuffers
+from .flat_state import FlatLayout, FlatTrainerState, Queue, bind_to_average, clip_decision  # noqa: F401  (Queue: this module's public name for it)
 from .loss import DiffusionLoss
 
 UNUSED_PREFIXES = ("model.distance_embedding.", "model.last_layer.")
 DEFAULT_OPTIMIZER = dict(lr=2.5e-4, betas=(0.9, 0.999), weight_decay=0, amsgrad=True)      # train_ts1x.py:66-71
-
-
-def bind_to_average(slots, tensors, flat_ema: Tensor, where: Dict[int, int]) -> None:
-    """Fills a shadow module (`DDPMTrainer.ema_dynamics`, `ConfidenceTrainer.ema_confidence`): slot k, an (owning module, attribute)
-    pair of the shadow, receives the live module's `tensors[k]` - as a VIEW into `flat_ema` at offset `where[id(tensor)]` if it is a
-    trained tensor, else the live tensor itself (shared storage).  A tensor that sits in several slots stays one object;
-    requires_grad is False throughout."""
-    made: Dict[int, Tensor] = {}
-    for (mod, attr), t in zip(slots, tensors):
-        new = made.get(id(t))
-        if new is None:
-            o = where.get(id(t))
-            data = t.detach() if o is None else flat_ema[o: o + t.numel()].view_as(t)
-            new = made[id(t)] = nn.Parameter(data, requires_grad=False) if isinstance(t, nn.Parameter) else data
-        if attr in mod._parameters:
-            mod._parameters[attr] = new
-        else:
-            mod._buffers[attr] = new
-
-
-class Queue:
-    """oa_reactdiff/utils/training_tools.py:6-23."""
-
-    def __init__(self, max_len: int = 50):
-        self.items: List[float] = []
-        self.max_len = max_len
-
-    def __len__(self):
-        return len(self.items)
-
-    def add(self, item: float) -> None:
-        self.items.insert(0, item)
-        if len(self) > self.max_len:
-            self.items.pop()
-
-    def mean(self) -> float:
-        return float(np.mean(self.items))
-
-    def std(self) -> float:
-        return float(np.std(self.items))
 
 
 class LazyInfo(Mapping):
@@ -115,7 +76,10 @@ class LazyInfo(Mapping):
         return len(self._get())
 
 
-class DDPMTrainer:
+class DDPMTrainer(FlatTrainerState):
+    CLIP_FACTORS = (1.5, 3.0)                          # pl_trainer.py:391-418: 150 % of the recent mean norm + 3 standard deviations
+    SKIP_MESSAGE = "Warning: non-finite loss / gradient / network output on some rank: step skipped on all ranks ({} so far)"
+
     def __init__(self, dynamics: nn.Module, noise_schedule: str = "polynomial_2", timesteps: int = 1000,
                  precision: float = 1e-5, norm_values: Sequence[float] = (1.0, 1.0, 1.0),
                  norm_biases: Sequence[float] = (0.0, 0.0, 0.0), loss_type: str = "l2", pos_only: bool = False,
@@ -173,25 +137,16 @@ class DDPMTrainer:
                 seen.add(id(p))
                 self.params.append(p)
                 self.names.append(name)
-        n = sum(p.numel() for p in self.params)
+        self._lay_out(1, ema_decay, clip_grad)         # no alignment padding; p.grad = view into the bucket: backward accumulates in place
+        n = self.layout.size
         # one bucket: [gradients (n) | non-finite flag (1)]; the flag rides in the same all-reduce so that every rank takes the
         # same skip / step decision after the collective (a rank that bails out BEFORE it would leave the others hanging)
         self._bucket = torch.zeros(n + 1, dtype=self.params[0].dtype, device=self.params[0].device)
-        self.flat_grad = self._bucket[:n]
-        self.skipped_steps = 0
-        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
-            raise ValueError(f"ema_decay must lie in [0, 1] (got {ema_decay!r})")
-        self.ema_decay = None if ema_decay is None else float(ema_decay)
-        self.flat_ema: Optional[Tensor] = None
         self._ema_dynamics = None                      # the shadow module, built at the first look at `ema_dynamics`
         self._ema_warned = False
         self._ema_view_list = None
         if self.collectives:
             self.sync_replicas()
-        off = 0
-        for p in self.params:                          # p.grad = view into the bucket: backward accumulates in place
-            p.grad = self.flat_grad[off: off + p.numel()].view_as(p)
-            off += p.numel()
         self.opt_config = dict(DEFAULT_OPTIMIZER, **(optimizer_config or {}))
         can_fuse = (hasattr(dynamics, "_get_packed_bwd") and self.params[0].device.type == "cuda" and loss_type == "l2"
                     and self.params[0].dtype == torch.float32)
@@ -206,29 +161,13 @@ class DDPMTrainer:
             # themselves become views of ONE flat buffer, so that AdamW is a single kernel over it (oard_adamw_step) and
             # state_dict() / load_state_dict() keep working on the same storage
             dynamics.grad_inplace = True
-            self.flat_param = torch.empty(n, dtype=torch.float32, device=self.flat_grad.device)
-            off = 0
-            with torch.no_grad():
-                for p in self.params:
-                    self.flat_param[off: off + p.numel()].copy_(p.reshape(-1))
-                    p.data = self.flat_param[off: off + p.numel()].view_as(p)
-                    off += p.numel()
-            self.exp_avg = torch.zeros_like(self.flat_param)
-            self.exp_avg_sq = torch.zeros_like(self.flat_param)
-            self.max_exp_avg_sq = torch.zeros_like(self.flat_param)
-            self.opt_step = 0
-        if self.ema_decay is not None:                 # ModelEmaV2.__init__: a copy of the weights (the replicas are synchronised by now)
-            self.flat_ema = self._flat_weights()
+        self._bind(self._bucket[:n], torch.empty(n, dtype=torch.float32, device=self._bucket.device) if self.fused else None)
         # `trainer.optimizer` is what the reference's configure_optimizers returns (pl_trainer.py:149-151): the generic path steps it;
         # the fused path runs oard_adamw_step on the flat buffers but reads lr / betas / eps / weight_decay / amsgrad from
         # `optimizer.param_groups[0]` at EVERY step, so an LR scheduler attached to it (or an edit of the group) takes effect in
         # both modes.  The fused moments live in `exp_avg` / `exp_avg_sq` / `max_exp_avg_sq` / `opt_step`: see state_dict().
         self.optimizer = torch.optim.AdamW(self.params, **self.opt_config)
         self._gamma_dev = None
-        self.clip_grad = clip_grad
-        if clip_grad:                                  # pl_trainer.py:143-146
-            self.gradnorm_queue = Queue()
-            self.gradnorm_queue.add(3000)
 
     # ---- resume: what Lightning's checkpoint keeps of the reference trainer (`optimizer_states`, pl_trainer.py:149-151; the clipping
     # history `gradnorm_queue` is NOT checkpointed by the reference and restarts at [3000], :143-146 - it is kept here) -------------
@@ -237,47 +176,24 @@ class DDPMTrainer:
         (fused: flat AdamW moments + step counter + the hyper-parameters of `optimizer.param_groups`; generic: torch's), the clipping
         history and the skipped-step counter."""
         self._pull_clip_state()
-        sd: Dict = {"fused": bool(self.fused), "names": list(self.names), "skipped_steps": int(self.skipped_steps),
-                    "gradnorm_queue": list(self.gradnorm_queue.items) if self.clip_grad else None}
-        if self.fused:
-            sd["opt_step"] = int(self.opt_step)
-            sd["param_groups"] = [{k: v for k, v in g.items() if k != "params"} for g in self.optimizer.param_groups]
-            for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"):
-                sd[k] = getattr(self, k).detach().clone()
-        else:
+        sd: Dict = {"fused": bool(self.fused), **super().state_dict()}
+        if not self.fused:
             sd["optimizer"] = copy.deepcopy(self.optimizer.state_dict())     # a snapshot: torch hands out the live moment tensors
-        if self.flat_ema is not None:                  # (no key at all without EMA: states of earlier versions and of EMA-less runs are the same)
-            sd["ema_decay"] = float(self.ema_decay)
-            sd["ema"] = self.flat_ema.detach().clone()
         return sd
 
     def load_state_dict(self, sd: Dict) -> None:
-        if list(sd["names"]) != list(self.names):
-            raise ValueError("trainer state belongs to a different parameter list")
-        if bool(sd["fused"]) != bool(self.fused):
+        if list(sd["names"]) == list(self.names) and bool(sd["fused"]) != bool(self.fused):      # (other names: the error below)
             raise ValueError(f"trainer state was saved with fused={sd['fused']}, this trainer runs fused={self.fused}")
+        super().load_state_dict(sd)
         self._clip_state = None                        # rebuilt from the host copies at the next sync-free step
-        self.skipped_steps = int(sd["skipped_steps"])
-        if self.clip_grad and sd.get("gradnorm_queue") is not None:
-            self.gradnorm_queue.items = [float(x) for x in sd["gradnorm_queue"]]
-        if self.fused:
-            self.opt_step = int(sd["opt_step"])
-            for g, saved in zip(self.optimizer.param_groups, sd["param_groups"]):
-                g.update(saved)
-            with torch.no_grad():
-                for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"):
-                    getattr(self, k).copy_(sd[k].to(self.flat_param.device))
-        else:
+        if not self.fused:
             self.optimizer.load_state_dict(sd["optimizer"])
-        if self.flat_ema is not None:                  # (a saved average is ignored by a trainer that keeps none)
-            with torch.no_grad():
-                if sd.get("ema") is not None:
-                    self.ema_decay = float(sd.get("ema_decay", self.ema_decay))
-                    self.flat_ema.copy_(sd["ema"].to(device=self.flat_ema.device, dtype=self.flat_ema.dtype))
-                else:                                  # the run that wrote this state kept no average: start one from the weights it resumes
-                    if not self._ema_warned:
-                        self._ema_warned = True
-                        warnings.warn("trainer state holds no EMA: the average restarts from the current weights")
+        if self.flat_ema is not None:
+            if sd.get("ema") is None:                  # the run that wrote this state kept no average: start one from the weights it resumes
+                if not self._ema_warned:
+                    self._ema_warned = True
+                    warnings.warn("trainer state holds no EMA: the average restarts from the current weights")
+                with torch.no_grad():
                     self.flat_ema.copy_(self._flat_weights())
             if self._ema_dynamics is not None:
                 self._ema_dynamics.invalidate_packed()
@@ -396,12 +312,6 @@ class DDPMTrainer:
         return mean, median
 
     # ---- the moving average of the weights (trainer/ema.py; see `ema_decay` in __init__) ---------------------------------------------------
-    def _flat_weights(self) -> Tensor:
-        """A fresh flat copy of the trainable weights in the bucket's order."""
-        if self.fused:
-            return self.flat_param.detach().clone()
-        return torch.cat([p.detach().reshape(-1) for p in self.params])
-
     def _need_ema(self) -> Tensor:
         if self.flat_ema is None:
             raise RuntimeError("this trainer keeps no EMA of the weights (DDPMTrainer(ema_decay=...))")
@@ -410,11 +320,7 @@ class DDPMTrainer:
     def _ema_views(self) -> List[Tensor]:
         """`flat_ema` as one view per trainable tensor (made once: the buffer is only ever written in place)."""
         if self._ema_view_list is None:
-            views, off = [], 0
-            for p in self.params:
-                views.append(self.flat_ema[off: off + p.numel()].view_as(p))
-                off += p.numel()
-            self._ema_view_list = views
+            self._ema_view_list = self.layout.views(self.flat_ema)
         return self._ema_view_list
 
     def _ema_step_generic(self) -> None:
@@ -446,10 +352,7 @@ class DDPMTrainer:
         forward never uses equal their average).  Names and shapes are the reference's: it loads with strict=True into the reference's
         EGNNDynamics or into a fresh one here."""
         ema = self._need_ema()
-        where, off = {}, 0
-        for p in self.params:
-            where[id(p)] = off
-            off += p.numel()
+        where = self.layout.offsets()
         out = OrderedDict()
         for name, t in self.dynamics.state_dict(keep_vars=True).items():
             o = where.get(id(t))
@@ -489,12 +392,8 @@ class DDPMTrainer:
             args = dict(args, model_config=dict(args["model_config"]), device=torch.device("meta"))     # nothing allocated: every tensor is replaced
             shadow = type(live)(**args)
             shadow.device = live.device
-            where, off = {}, 0
-            for p in self.params:
-                where[id(p)] = off
-                off += p.numel()
             shadow._ordered_tensors()                  # resolves the (owning module, attribute) pair of every state-dict entry
-            bind_to_average(shadow._slots[1], live._ordered_tensors(), ema, where)
+            bind_to_average(shadow._slots[1], live._ordered_tensors(), ema, self.layout.offsets())
             shadow.edge_precision, shadow.train_edge_precision = live.edge_precision, live.train_edge_precision
             shadow.nan_check, shadow.edge_list_path = live.nan_check, live.edge_list_path
             shadow.eval()
@@ -519,10 +418,8 @@ class DDPMTrainer:
                     continue
                 flat = torch.cat([t.reshape(-1).to(torch.float64 if t.dtype == torch.float64 else torch.float32) for t in uniq])
                 dist.broadcast(flat, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
-                off = 0
-                for t in uniq:
-                    t.copy_(flat[off: off + t.numel()].view_as(t))      # in place: bumps the version -> weights are repacked
-                    off += t.numel()
+                for t, received in zip(uniq, FlatLayout(uniq).views(flat)):
+                    t.copy_(received)                      # in place: bumps the version -> weights are repacked
                 if check:                                  # cheap invariant: every rank now holds the same bytes
                     cs = flat.double().abs().sum().reshape(1)
                     lo, hi = cs.clone(), cs.clone()
@@ -569,18 +466,12 @@ class DDPMTrainer:
 
     def clip_gradients(self, grad_norm: Optional[float] = None) -> Tuple[float, float]:
         """pl_trainer.py:391-418: allow 150 % of the recent mean norm + 3 standard deviations."""
-        max_grad_norm = 1.5 * self.gradnorm_queue.mean() + 3 * self.gradnorm_queue.std()
         # get_grad_norm (training_tools.py:29-55): 2-norm of the per-parameter 2-norms == 2-norm of the flat bucket
         if grad_norm is None:
             grad_norm = float(torch.linalg.vector_norm(self.flat_grad, 2.0))
-        if not math.isfinite(grad_norm):                # never poison the history of norms (nan > max is False: clipping would stay off)
-            return grad_norm, max_grad_norm
-        if grad_norm > max_grad_norm:                  # clip_grad_norm_: g *= max_norm / (norm + 1e-6)
-            self.flat_grad.mul_(max_grad_norm / (grad_norm + 1e-6))
-            self.gradnorm_queue.add(float(max_grad_norm))
-            print(f"Clipped gradient with value {grad_norm:.1f} while allowed {max_grad_norm:.1f}")
-        else:
-            self.gradnorm_queue.add(grad_norm)
+        gscale, max_grad_norm = clip_decision(self.gradnorm_queue, grad_norm, *self.CLIP_FACTORS)
+        if math.isfinite(grad_norm) and grad_norm > max_grad_norm:      # (a non-finite norm: nothing scaled, nothing remembered)
+            self.flat_grad.mul_(gscale)                # clip_grad_norm_: g *= max_norm / (norm + 1e-6)
         return grad_norm, max_grad_norm
 
     # ---- fused step (HIP module): no autograd graph, ~20 launches around the network call ----------------------------------------
@@ -639,12 +530,8 @@ class DDPMTrainer:
             with torch.cuda.device(dev):
                 _capi.check(_capi.lib().oard_library_stream(1, C.byref(h)), "oard_library_stream")
             grad2 = torch.zeros_like(self.flat_grad)
-            dests2, off = {}, 0
-            for p in self.params:
-                dests2[id(p)] = grad2[off: off + p.numel()].view_as(p)
-                off += p.numel()
-            self._mb = {"device": dev, "stream": torch.cuda.ExternalStream(h.value, device=dev), "grad": grad2, "dests": dests2,
-                        "buffers": _CallBuffers()}
+            self._mb = {"device": dev, "stream": torch.cuda.ExternalStream(h.value, device=dev), "grad": grad2,
+                        "dests": self.layout.dests(grad2), "buffers": _CallBuffers()}
         return self._mb
 
     def _fused_forward_backward(self, batch, t_int: Optional[Tensor] = None, draw=None):
@@ -731,22 +618,8 @@ class DDPMTrainer:
             dyn.nan_seen.bitwise_or_(buf1.nan_seen)       # the second half's flag reaches the module's, which the step reads
         return torch.cat([nll0, nll1]), terms
 
-    def _adamw(self, entry: str, before, after) -> None:
-        """One call of the AdamW entry point `entry` - its `_ema` form when the trainer keeps an average - on the flat bucket with the
-        optimiser's hyper-parameters.  `before` / `after`: the entry point's own arguments on either side of `amsgrad`.  The weights
-        change behind torch's version counters (unless the device skipped the step: repacking is harmless)."""
-        o = self.optimizer.param_groups[0]
-        dev = self.flat_grad.device
-        args = (self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self.max_exp_avg_sq.data_ptr(), self.flat_param.numel(), float(o["lr"]), float(o["betas"][0]), float(o["betas"][1]),
-                float(o.get("eps", 1e-8)), float(o.get("weight_decay", 0.0)), *before, 1 if o.get("amsgrad", False) else 0, *after)
-        if self.flat_ema is not None:
-            entry, args = entry + "_ema", args + (self.flat_ema.data_ptr(), self.ema_decay)
-        with torch.cuda.device(dev):
-            _capi.check(getattr(_capi.lib(), entry)(*args, torch.cuda.current_stream(dev).cuda_stream), entry)
-        self.dynamics.invalidate_packed()
-        if self._ema_dynamics is not None:
-            self._ema_dynamics.invalidate_packed()
+    def _weight_readers(self):
+        return self.dynamics, self._ema_dynamics
 
     def _fused_step(self, batch, **kw) -> Dict[str, float]:
         dyn = self.dynamics
@@ -790,20 +663,10 @@ class DDPMTrainer:
         skipped = flag != 0 or not math.isfinite(grad_norm)
         gscale = 1.0
         if skipped:
-            self.skipped_steps += 1
-            print(f"Warning: non-finite loss / gradient / network output on some rank: step skipped on all ranks "
-                  f"({self.skipped_steps} so far)")
-            if self.clip_grad:
-                info["grad_norm"], info["max_grad_norm"] = grad_norm, float("nan")
+            self._count_skip(info, grad_norm)
         else:
             if self.clip_grad:                        # pl_trainer.py:391-418, with the factor folded into the optimiser kernel
-                max_norm = 1.5 * self.gradnorm_queue.mean() + 3 * self.gradnorm_queue.std()
-                if grad_norm > max_norm:
-                    gscale = max_norm / (grad_norm + 1e-6)
-                    self.gradnorm_queue.add(float(max_norm))
-                    print(f"Clipped gradient with value {grad_norm:.1f} while allowed {max_norm:.1f}")
-                else:
-                    self.gradnorm_queue.add(grad_norm)
+                gscale, max_norm = clip_decision(self.gradnorm_queue, grad_norm, *self.CLIP_FACTORS)
                 info["grad_norm"], info["max_grad_norm"] = grad_norm, max_norm
             self.opt_step += 1
             self._adamw("oard_adamw_step", (self.opt_step,), (float(gscale),))
@@ -851,11 +714,7 @@ class DDPMTrainer:
         grad_norm, flag, loss_value = stats
         skipped = flag != 0 or not math.isfinite(grad_norm)
         if skipped:
-            self.skipped_steps += 1
-            print(f"Warning: non-finite loss / gradient / network output on some rank: step skipped on all ranks "
-                  f"({self.skipped_steps} so far)")
-            if self.clip_grad:
-                info["grad_norm"], info["max_grad_norm"] = grad_norm, float("nan")
+            self._count_skip(info, grad_norm)
         else:
             if self.clip_grad:
                 info["grad_norm"], info["max_grad_norm"] = self.clip_gradients(grad_norm)

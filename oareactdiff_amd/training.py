@@ -30,6 +30,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _capi
+from .flat_state import FlatLayout
 
 UNUSED_PREFIXES = ("model.distance_embedding.", "model.last_layer.")
 
@@ -190,6 +191,25 @@ class _StageTimer:
         print("backward sweep ms: " + "  ".join(f"{k} {v:.2f}" for k, v in tot.items()) + f"  | total {sum(tot.values()):.2f}")
 
 
+def fresh_gradients(params: Dict[str, Tensor], dev) -> Tuple[Dict[str, Tensor], Dict[int, Tensor]]:
+    """Gradient destinations of a sweep whose caller keeps none: one fresh zero-filled flat float32 buffer laid out like `params`
+    (name -> tensor) -> ({name: view}, {id(tensor): view})."""
+    layout = FlatLayout(list(params.values()))
+    views = layout.views(torch.zeros(layout.size, dtype=torch.float32, device=dev))
+    return dict(zip(params, views)), {id(p): v for p, v in zip(layout.tensors, views)}
+
+
+def inplace_gradients(params: Dict[str, Tensor]) -> Dict[int, Tensor]:
+    """`grad_inplace`: the `.grad` tensors of `params` (name -> tensor) as gradient destinations {id(tensor): .grad}; a missing one is
+    created zero-filled, and each has to be contiguous float32 for the kernels to accumulate into."""
+    for n, p in params.items():
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        if p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
+            raise _capi.OardError(f"grad_inplace needs contiguous float32 .grad tensors ({n})")
+    return {id(p): p.grad for p in params.values()}
+
+
 def gradient_table(dyn, dests: Dict[int, Tensor]):
     """(void* array in the canonical parameter order of oard_pack_weights) for the gradient destinations: `dests` maps id(param) ->
     contiguous float32 tensor of the parameter's shape; parameters without an entry, buffers and the two modules the forward
@@ -228,16 +248,9 @@ class Sweep:
         if conf_tail is not None and dests is None:
             raise ValueError("a confidence sweep needs its gradient destinations")
         if dests is None:
-            names = dyn._param_names()
             P = dyn._param_dict()
-            used = [n for n in names if not n.startswith(UNUSED_PREFIXES)]
-            flat = torch.zeros(sum(P[n].numel() for n in used), dtype=torch.float32, device=dev)
-            dests, off = {}, 0
-            for n in used:
-                p = P[n]
-                self.out[n] = flat[off: off + p.numel()].view_as(p)
-                dests[id(p)] = self.out[n]
-                off += p.numel()
+            used = [n for n in dyn._param_names() if not n.startswith(UNUSED_PREFIXES)]
+            self.out, dests = fresh_gradients({n: P[n] for n in used}, dev)
         tensors = dyn._ordered_tensors()
         self.params = _capi.ptr_array(tensors)
         self.grads = gradient_table(dyn, dests)
@@ -321,16 +334,7 @@ class DynamicsFunction(torch.autograd.Function):
         P = dyn._param_dict()
         dests = None
         if dyn.grad_inplace:
-            dests = {}
-            for n in ctx.names:
-                p = P[n]
-                if n.startswith(UNUSED_PREFIXES):
-                    continue
-                if p.grad is None:
-                    p.grad = torch.zeros_like(p)
-                if p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
-                    raise _capi.OardError(f"grad_inplace needs contiguous float32 .grad tensors ({n})")
-                dests[id(p)] = p.grad
+            dests = inplace_gradients({n: P[n] for n in ctx.names if not n.startswith(UNUSED_PREFIXES)})
         with torch.cuda.device(dev), torch.no_grad():
             stream = torch.cuda.current_stream(dev).cuda_stream
             grads = backward_sweep(dyn, st, list(grad_outs), stream, dests)
