@@ -504,6 +504,42 @@ int oard_adamw_step(float* param_dev, const float* grad_dev, float* exp_avg_dev,
                     int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, int amsgrad,
                     double grad_scale, oard_stream_t stream);
 
+/* ---- The evaluation half of the loss: the variational bound of a validation batch (csrc/oard_loss_eval.h) ---------------------------
+ * oard_loss_prepare / oard_loss_terms above are the l2 training form only.  These two are the `not self.training` branch of
+ * EnVariationalDiffusion.forward (en_diffusion.py:56-248: a separate t = 0 call on its own noise, :181-199) and the `vlb` form of
+ * DDPMModule.compute_loss (pl_trainer.py:246-282), with TWO inference network calls (at t and at 0) between them.
+ * oard_loss_eval_prepare  en_diffusion.py:56-123 and :181-186 (noised_representation :250-281, sample_combined_position_feature_noise
+ *                    :283-306, both times) in ONE launch: normalises the dataset-layout batch once, removes the per-(sample, object) CoM
+ *                    of each of the two raw N(0,1) noise blocks, z_t = alpha_t x + sigma_t eps_t with gamma_t = gamma_table[t_int[b]],
+ *                    z_0 = alpha_0 x + sigma_0 eps_0 with gamma_0 = gamma_table[0].  pos_only / fixed_mask zero the noise exactly as
+ *                    oard_loss_prepare does.
+ * oard_loss_eval_terms    en_diffusion.py:125-248 (helpers :308-449) + pl_trainer.py:246-282: per-sample
+ *                      nll [B] = sum_k(-T/2 SNR_weight error_t_k) + sum_k(loss_0_x + loss_0_cat + loss_0_charge)_k + neg_log_constants
+ *                                - delta_log_px                                   (kl_prior = log_pN = 0), summed in double, rounded once
+ *                    and terms [5 n_obj + 2][B] with K = n_obj: rows [0, K) error_t per object normalised and scaled (info["error_t_k"]
+ *                    is its mean / (scales[k] + 1e-4)), [K, 2K) error_t un-normalised, [2K, 3K) loss_0_x, [3K, 4K) loss_0_cat, [4K, 5K)
+ *                    loss_0_charge, row 5K SNR_weight, row 5K + 1 neg_log_constants.  `B` is the row stride of `terms`; a call owns the
+ *                    columns its t_int rows name, so a part of a larger table passes terms_dev + col0 (as oard_loss_terms).  error_t is
+ *                    not masked and EVERY sample gets the t = 0 likelihood terms on z_0.  An empty (sample, object) group contributes 0
+ *                    and gets exact zeros in its five entries; only the normalised row divides by a size.
+ * snr_dev [T+1] (device, float32): SNR_weight per time step, 1 - exp(-(gamma[t-1] - gamma[t])) evaluated by the HOST in float64 and
+ * rounded once (in float32 most digits of the ~1e-3 difference cancel).  Entry 0 is never read for valid input: in evaluation t_int lies
+ * in [1, T].  Every index into the gamma and SNR tables is clamped into [0, T], so an out-of-contract t_int reads no other memory.
+ * delta_log_px: the host scalar -(N_atoms_of_the_batch - 1) * 3 * log(norm_values[0]) (en_diffusion.py:87-89: the whole-batch quantity).
+ * Returned before any HIP call, with OARD_EINVAL: a null table or pointer list, B < 1, T < 1, n_obj outside [1, OARD_MAX_OBJECTS],
+ * node_nf - 4 outside [1, 16], an unbuilt configuration, a topology of more than one sub-batch. */
+int oard_loss_eval_prepare(const oard_config* cfg, const oard_topology* topo, const float* const* pos_dev,
+                           const int64_t* const* one_hot_dev, const int64_t* const* charge_dev, const float* const* noise_t_dev,
+                           const float* const* noise_0_dev, const float* t_int_dev, const float* gamma_dev, int T,
+                           const float* norm_values, const float* norm_biases, int pos_only, int fixed_mask, float* const* z_t_dev,
+                           float* const* eps_t_dev, float* const* z_0_dev, float* const* eps_0_dev, oard_stream_t stream);
+int oard_loss_eval_terms(const oard_config* cfg, const oard_topology* topo, const float* const* eps_t_dev,
+                         const float* const* net_t_dev, const float* const* eps_0_dev, const float* const* net_0_dev,
+                         const float* const* z_0_dev, const int64_t* const* one_hot_dev, const int64_t* const* charge_dev,
+                         const float* t_int_dev, const float* gamma_dev, const float* snr_dev, int T, const float* norm_values,
+                         const float* norm_biases, const float* scales, int pos_only, double delta_log_px, int B, float* nll_dev,
+                         float* terms_dev, oard_stream_t stream);
+
 /* The optimiser step WITHOUT a host round trip (round 4): the adaptive clipping decision of pl_trainer.py:391-418 (max_norm = 1.5 mean +
  * 3 std of the last <= `capacity` gradient norms, utils/training_tools.py:6-23) taken by one device thread, then AdamW with the scalars it
  * derived.  clip_state (device, doubles, 4 + capacity + 8 entries): [0] entries in the history, [1] optimiser steps taken so far, [2] steps

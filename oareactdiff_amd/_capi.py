@@ -8,7 +8,7 @@ import os
 from .build import LIB
 
 OARD_MAX_OBJECTS = 8
-ABI_VERSION = 2046            # OARD_VERSION of csrc/oard_hip.hip (checked by lib(): a stale library is refused, not misread)
+ABI_VERSION = 2047            # OARD_VERSION of csrc/oard_hip.hip (checked by lib(): a stale library is refused, not misread)
 OARD_OK, OARD_EINVAL, OARD_ENOTCOMPLETE, OARD_EHIP, OARD_ENOMEM = 0, -1, -2, -3, -4
 ERRORS = {OARD_EINVAL: "invalid argument / unsupported configuration", OARD_ENOTCOMPLETE: "topology is not complete-per-sample",
           OARD_EHIP: "HIP runtime error", OARD_ENOMEM: "workspace too small"}
@@ -26,7 +26,7 @@ EXPORTS = ["oard_version", "oard_supported", "oard_param_count", "oard_packed_by
            "oard_equi_backward_dx", "oard_scalarize_backward", "oard_equi_msg_backward", "oard_lin3u_forward", "oard_lin3u_backward", "oard_wgrad_scratch_bytes", "oard_wgrad",
            "oard_train_scratch_bytes", "oard_train_scratch_poison", "oard_train_scratch_entry", "oard_train_tail_backward",
            "oard_train_layer_backward", "oard_train_init_backward", "oard_train_stage_backward",
-           "oard_loss_prepare", "oard_loss_terms", "oard_adamw_step", "oard_adamw_step_dev", "oard_nan_replace",
+           "oard_loss_prepare", "oard_loss_terms", "oard_loss_eval_prepare", "oard_loss_eval_terms", "oard_adamw_step", "oard_adamw_step_dev", "oard_nan_replace",
            "oard_adamw_step_ema", "oard_adamw_step_dev_ema", "oard_ema_update", "oard_kabsch_rmsd", "oard_matched_rmsd", "oard_rank_metrics",
            "oard_graph_create", "oard_graph_destroy", "oard_graph_num_nodes", "oard_graph_num_edges", "oard_graph_object_rows",
            "oard_graph_is_complete", "oard_graph_workspace_bytes", "oard_graph_forward", "oard_library_stream",
@@ -154,6 +154,10 @@ def lib() -> C.CDLL:
     L.oard_loss_prepare.argtypes = [cfgp, vp, pvp, pvp, pvp, pvp, vp, vp, ci, pf, pf, ci, ci, pvp, pvp, vp]; L.oard_loss_prepare.restype = ci
     L.oard_loss_terms.argtypes = [cfgp, vp, pvp, pvp, pvp, pvp, pvp, vp, vp, ci, pf, pf, pf, ci, ci, vp, vp, pvp, vp]; L.oard_loss_terms.restype = ci
     cd = C.c_double
+    L.oard_loss_eval_prepare.argtypes = [cfgp, vp, pvp, pvp, pvp, pvp, pvp, vp, vp, ci, pf, pf, ci, ci, pvp, pvp, pvp, pvp, vp]
+    L.oard_loss_eval_prepare.restype = ci
+    L.oard_loss_eval_terms.argtypes = [cfgp, vp, pvp, pvp, pvp, pvp, pvp, pvp, pvp, vp, vp, vp, ci, pf, pf, pf, ci, cd, ci, vp, vp, vp]
+    L.oard_loss_eval_terms.restype = ci
     L.oard_adamw_step.argtypes = [vp, vp, vp, vp, vp, i64, cd, cd, cd, cd, cd, i64, ci, cd, vp]; L.oard_adamw_step.restype = ci
     L.oard_adamw_step_dev.argtypes = [vp, vp, vp, vp, vp, i64, cd, cd, cd, cd, cd, ci, ci, vp, ci, vp, vp, vp, vp]; L.oard_adamw_step_dev.restype = ci
     L.oard_adamw_step_ema.argtypes = [vp, vp, vp, vp, vp, i64, cd, cd, cd, cd, cd, i64, ci, cd, vp, cd, vp]; L.oard_adamw_step_ema.restype = ci

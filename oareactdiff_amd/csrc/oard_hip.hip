@@ -29,7 +29,7 @@
 #include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
-#define OARD_VERSION 2046      // + oard_rank_metrics (2045: oard_matched_rmsd; 2044: oard_confidence_forward_train, oard_confidence_tail_backward; 2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
+#define OARD_VERSION 2047      // + oard_loss_eval_prepare, oard_loss_eval_terms (2046: oard_rank_metrics; 2045: oard_matched_rmsd; 2044: oard_confidence_forward_train, oard_confidence_tail_backward; 2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
 // The first-generation kernels (weights straight from L2, one wave per 16 nodes: gcl_variant / equi_variant / node_variant 0) are the
 // A/B baseline of round 1 and a cross-check in tests/test_hip_parity.py::test_every_kernel_variant_is_parity_green; they are compiled
 // into experiment builds (-DOARD_EXPERIMENTS) only - a product library refuses those variants (oard_debug_option returns OARD_EINVAL).
@@ -2215,6 +2215,7 @@ int oard_wgrad(const float* dY, int ldY, int ncY, int o_len, int o_pad, int MO, 
 }  // extern "C"
 #include "oard_train_stages.h"
 #include "oard_loss.h"
+#include "oard_loss_eval.h"
 #include "oard_kabsch.h"     // k_kabsch_rmsd: the validation metric (oard_kabsch_rmsd)
 #include "oard_match.h"      // k_matched_rmsd: the same with the atoms matched first (oard_matched_rmsd)
 #include "oard_rank.h"       // k_rank_count, k_rank_stats: midranks per segment, AUROC / Pearson / Spearman (oard_rank_metrics)
@@ -2415,6 +2416,56 @@ int oard_loss_terms(const oard_config* c, const oard_topology* topo, const float
     const TopoDev& tp = topo->parts[0].d;
     LAUNCH(F_OTHER, k_loss_terms, tp.B, 64, (hipStream_t)stream, tp, lp, make_loss_cfg(c, norm_values, norm_biases, scales, pos_only, 0, T),
            t_int, gamma, B, nll, terms);
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+// ---- the evaluation half: both noised representations in one launch, the VLB terms per sample (oard_loss_eval.h) ---------------------
+// every argument check comes before the first HIP call (topo_touch included): a refused call touches neither the device nor the topology
+static bool loss_eval_args_ok(const oard_config* c, const oard_topology* topo, int T) {
+    if (!c || !topo || T <= 0) return false;
+    if (c->n_obj < 1 || c->n_obj > OARD_MAX_OBJECTS) return false;
+    for (int k = 0; k < c->n_obj; ++k)
+        if (c->node_nf[k] < 5 || c->node_nf[k] - 4 > 16) return false;            // [pos 3 | one_hot 1 .. 16 | charge 1]
+    return config_ok(c) && topo->n_parts == 1 && c->n_obj == topo->n_obj;
+}
+int oard_loss_eval_prepare(const oard_config* c, const oard_topology* topo, const float* const* pos, const int64_t* const* one_hot,
+                           const int64_t* const* charge, const float* const* noise_t, const float* const* noise_0, const float* t_int,
+                           const float* gamma, int T, const float* norm_values, const float* norm_biases, int pos_only, int fixed_mask,
+                           float* const* z_t, float* const* eps_t, float* const* z_0, float* const* eps_0, oard_stream_t stream) {
+    if (!pos || !one_hot || !charge || !noise_t || !noise_0 || !t_int || !gamma || !z_t || !eps_t || !z_0 || !eps_0) return OARD_EINVAL;
+    if (!loss_eval_args_ok(c, topo, T)) return OARD_EINVAL;
+    topo_touch(topo, (hipStream_t)stream);
+    EvalPrepPtrs ep;
+    memset(&ep, 0, sizeof(ep));
+    for (int k = 0; k < c->n_obj; ++k) {
+        ep.pos[k] = pos[k]; ep.one_hot[k] = (const long long*)one_hot[k]; ep.charge[k] = (const long long*)charge[k];
+        ep.noise_t[k] = noise_t[k]; ep.noise_0[k] = noise_0[k]; ep.z_t[k] = z_t[k]; ep.eps_t[k] = eps_t[k]; ep.z_0[k] = z_0[k];
+        ep.eps_0[k] = eps_0[k]; ep.node_nf[k] = c->node_nf[k];
+    }
+    const TopoDev& tp = topo->parts[0].d;
+    LAUNCH(F_OTHER, k_eval_prep, cdiv(tp.N, 128), 128, (hipStream_t)stream, tp, ep,
+           make_loss_cfg(c, norm_values, norm_biases, nullptr, pos_only, fixed_mask, T), t_int, gamma);
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+int oard_loss_eval_terms(const oard_config* c, const oard_topology* topo, const float* const* eps_t, const float* const* net_t,
+                         const float* const* eps_0, const float* const* net_0, const float* const* z_0, const int64_t* const* one_hot,
+                         const int64_t* const* charge, const float* t_int, const float* gamma, const float* snr, int T,
+                         const float* norm_values, const float* norm_biases, const float* scales, int pos_only, double delta_log_px, int B,
+                         float* nll, float* terms, oard_stream_t stream) {
+    if (!eps_t || !net_t || !eps_0 || !net_0 || !z_0 || !one_hot || !charge || !t_int || !gamma || !snr || !nll || !terms || B < 1)
+        return OARD_EINVAL;
+    if (!loss_eval_args_ok(c, topo, T)) return OARD_EINVAL;
+    topo_touch(topo, (hipStream_t)stream);
+    VlbPtrs vp;
+    memset(&vp, 0, sizeof(vp));
+    for (int k = 0; k < c->n_obj; ++k) {
+        vp.eps_t[k] = eps_t[k]; vp.net_t[k] = net_t[k]; vp.eps_0[k] = eps_0[k]; vp.net_0[k] = net_0[k]; vp.z_0[k] = z_0[k];
+        vp.one_hot[k] = (const long long*)one_hot[k]; vp.charge[k] = (const long long*)charge[k]; vp.node_nf[k] = c->node_nf[k];
+    }
+    const TopoDev& tp = topo->parts[0].d;
+    LAUNCH(F_OTHER, k_vlb_terms, tp.B, 64, (hipStream_t)stream, tp, vp, make_loss_cfg(c, norm_values, norm_biases, scales, pos_only, 0, T),
+           t_int, gamma, snr, delta_log_px, B, nll, terms);
     HIP_TRY(hipGetLastError());
     return OARD_OK;
 }

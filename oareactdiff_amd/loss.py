@@ -10,7 +10,9 @@ The network call is `oareactdiff_amd.EGNNDynamics` (HIP); everything around it i
 and segmented-sum torch ops on [N, 9] tensors that stay on the device.  With `training=True` the terms are
 differentiable: under autograd the network call runs the training-mode HIP forward and `loss.backward()` reaches
 the parameters through `oareactdiff_amd.training.DynamicsFunction` (hand-written backward of the edge stages).
-Evaluation (`training=False`, what `validation_step` takes) never needs gradients and runs under `torch.no_grad()`.
+Evaluation (`training=False`) never needs gradients and runs under `torch.no_grad()`.  It is the general formulation of the validation
+loss, not what `DDPMTrainer.validation_step` runs on a ROCm device: that takes the two fused kernels of csrc/oard_loss_eval.h
+(`DDPMTrainer.eval_loss`) and falls back to this class only where it cannot fuse (CPU, a network that is not the HIP module).
 """
 from __future__ import annotations
 
@@ -195,6 +197,12 @@ class DiffusionLoss:
         (pl_trainer.py:268-277) is a host sync between the forward and the backward pass, during which the GPU runs dry while
         the host enqueues the first backward kernels; DDPMTrainer.training_step converts them after the optimiser step."""
         lt = self.loss_terms(representations, conditions, training=training, t_int=t_int, draw=draw)
+        return self.nll_and_info(lt, representations, training, lazy_info)
+
+    def nll_and_info(self, lt: Dict, representations: List[Dict[str, Tensor]], training: bool,
+                     lazy_info: bool = False) -> Tuple[Tensor, Dict[str, float]]:
+        """pl_trainer.py:236-282 on a `loss_terms` dict: the per-sample nll and the logged means (what `compute_loss` returns; a caller
+        that also needs the terms themselves - DDPMTrainer.eval_loss off the device path - pays the network calls once)."""
         K = len(representations)
         width = [self.pos_dim if self.pos_only else self.pos_dim + self.node_nfs[k] for k in range(K)]
         denoms = [width[k] * representations[k]["size"] for k in range(K)]

@@ -43,6 +43,17 @@ UNUSED_PREFIXES = ("model.distance_embedding.", "model.last_layer.")
 DEFAULT_OPTIMIZER = dict(lr=2.5e-4, betas=(0.9, 0.999), weight_decay=0, amsgrad=True)      # train_ts1x.py:66-71
 
 
+def vlb_snr_table(schedule) -> Tensor:
+    """SNR_weight of every time step, float32 [T + 1]: entry t = 1 - exp(-(gamma[t - 1] - gamma[t])) (en_diffusion.py:139-140 with
+    s = t - 1/T), evaluated in float64 on the schedule's gamma table widened to float64 - what the reference's float64 run sees - and
+    rounded once.  In float32 most digits of the ~1e-3 difference cancel.  Entry 0 is 0 and is never read for valid input: in
+    evaluation t_int lies in [1, T] (the reference's own lookup at t = 0 would wrap around to gamma[T])."""
+    g = schedule.gamma.double().numpy()
+    out = np.zeros(g.shape[0], dtype=np.float64)
+    out[1:] = -np.expm1(-(g[:-1] - g[1:]))
+    return torch.from_numpy(out.astype(np.float32))
+
+
 class LazyInfo(Mapping):
     """What `training_step` returns with `host_sync=False`: the same keys as the eager dict (loss, skipped, grad_norm, max_grad_norm,
     error_t_k, unorm_error_t_k), held as two small device tensors and copied to the host the first time any of them is read."""
@@ -168,6 +179,9 @@ class DDPMTrainer(FlatTrainerState):
         # both modes.  The fused moments live in `exp_avg` / `exp_avg_sq` / `max_exp_avg_sq` / `opt_step`: see state_dict().
         self.optimizer = torch.optim.AdamW(self.params, **self.opt_config)
         self._gamma_dev = None
+        self._snr_dev = None                           # SNR_weight per time step (vlb_snr_table), uploaded at the first eval_loss
+        self._val_div: Dict[tuple, Tensor] = {}        # the divisors of validation_step's logged means, per (device, dtype)
+        self._val_kept: Dict[str, Tuple[List[Tensor], List[Tensor]]] = {}      # prefix -> (rows, per-reaction nll) since the last epoch end
 
     # ---- resume: what Lightning's checkpoint keeps of the reference trainer (`optimizer_states`, pl_trainer.py:149-151; the clipping
     # history `gradnorm_queue` is NOT checkpointed by the reference and restarts at [3000], :143-146 - it is kept here) -------------
@@ -310,6 +324,177 @@ class DDPMTrainer(FlatTrainerState):
             median = torch.where(cnt > 0, median, torch.full_like(median, float("nan")))
             mean, median = torch.stack([mean, median]).tolist()                                  # the one read of the two scalars
         return mean, median
+
+    # ---- validation: the variational bound of a batch on the device, the epoch's means (pl_trainer.py:349-382, `_shared_eval`) --------------
+    def _can_eval_fused(self) -> bool:
+        """The two evaluation kernels need what the fused step needs except the l2 objective: the HIP module on a ROCm device, float32."""
+        return (hasattr(self.dynamics, "_get_packed_bwd") and self.params[0].device.type == "cuda"
+                and self.params[0].dtype == torch.float32)
+
+    def eval_loss(self, batch, weights: str = "live", t_int: Optional[Tensor] = None, draw=None) -> Tuple[Tensor, Tensor]:
+        """The evaluation half of `EnVariationalDiffusion.forward` + `DDPMModule.compute_loss` (en_diffusion.py:56-248,
+        pl_trainer.py:246-282) -> (nll [B], terms [5 K + 2, B]), both on the device, for K objects:
+            rows [0, K) error_t per object, normalised and scaled   [K, 2K) error_t   [2K, 3K) loss_0_x   [3K, 4K) loss_0_cat
+            [4K, 5K) loss_0_charge   row 5K SNR_weight   row 5K + 1 neg_log_constants
+            nll = sum_k(-T/2 SNR_weight error_t_k) + sum_k(loss_0_x + loss_0_cat + loss_0_charge)_k + neg_log_constants - delta_log_px
+        On a ROCm device with the HIP module: `oard_loss_eval_prepare` (ONE launch for z_t and z_0), two inference network calls (at t
+        and at 0: the non-taping `oard_forward`, no gradient work) on the layout built from the batch's host copies of mask / size when
+        `to_device` kept them, `oard_loss_eval_terms` - no device -> host read.  `t_int` is drawn with randint(1, T + 1) on the device
+        and must lie in [1, T]; the noise of both representations is ONE randn.  Injected `draw` follows DiffusionLoss's protocol: per
+        object (n, 3) then (n, nf - 3) for z_t, then the same again for z_0.  `weights="ema"` runs `ema_dynamics` (ValueError on a
+        trainer without `ema_decay`).  An empty (sample, object) group contributes 0 (DiffusionLoss gives NaN there).
+        Anywhere else (CPU, a network that is not the HIP module): the same table from `DiffusionLoss.loss_terms(training=False)`.
+        Changes no weight, no optimiser, clip or EMA state, and neither the module's `training` flag nor its `nan_check`."""
+        if weights not in ("live", "ema"):
+            raise ValueError(f"weights must be 'live' or 'ema' (got {weights!r})")
+        if weights == "ema" and self.flat_ema is None:
+            raise ValueError("this trainer keeps no average of the weights (DDPMTrainer(ema_decay=...))")
+        dyn = self.dynamics if weights == "live" else self.ema_dynamics
+        if self._can_eval_fused():
+            return self._eval_loss_fused(dyn, batch, t_int, draw)
+        reps, cond = batch
+        ls = self.loss
+        ls.dynamics = dyn
+        try:
+            lt = ls.loss_terms(reps, cond, training=False, t_int=t_int, draw=draw)
+        finally:
+            ls.dynamics = self.dynamics
+        nll, _ = ls.nll_and_info(lt, reps, training=False, lazy_info=True)
+        K = len(reps)
+        width = [ls.pos_dim if ls.pos_only else ls.pos_dim + ls.node_nfs[k] for k in range(K)]
+        err_n = [lt["error_t"][k] / (width[k] * reps[k]["size"]) * ls.scales[k] for k in range(K)]
+        rows = err_n + [lt[key][k] for key in ("error_t", "loss_0_x", "loss_0_cat", "loss_0_charge") for k in range(K)]
+        return nll, torch.stack(rows + [lt["SNR_weight"], lt["neg_log_constants"]])
+
+    def _infer(self, dyn, cfg, topo, packed: Tensor, xh: List[Tensor], t: Tensor, cond, stream: int) -> List[Tensor]:
+        """One inference network call (`oard_forward`: no tape) on the single-sub-batch topology the loss kernels share."""
+        L = _capi.lib()
+        dev = xh[0].device
+        xs, tt, t_scalar, cnd = dyn._inputs(topo, xh, t, cond, dev, detach=True)
+        outs = [torch.empty_like(x) for x in xs]
+        ws = dyn._call_buffers.workspace(L.oard_workspace_bytes(C.byref(cfg), topo.handle), dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        _capi.check(L.oard_forward(C.byref(cfg), topo.handle, packed.data_ptr(), _capi.ptr_array(xs), tt.data_ptr(), t_scalar,
+                                   cnd.data_ptr() if cnd is not None else None, _capi.ptr_array(outs), ws.data_ptr(), ws.numel(),
+                                   status.data_ptr(), stream), "oard_forward")
+        return outs
+
+    def _eval_loss_fused(self, dyn, batch, t_int: Optional[Tensor], draw) -> Tuple[Tensor, Tensor]:
+        reps, cond = batch
+        ls = self.loss
+        dev = self.flat_grad.device
+        K = len(reps)
+        L = _capi.lib()
+        masks, sizes = [r["mask"] for r in reps], [r["size"] for r in reps]
+        have_host = all("mask_host" in r and "size_host" in r for r in reps)
+        B = int(sizes[0].numel())
+        with torch.cuda.device(dev), torch.no_grad():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            cfg = dyn._config()
+            _capi.check(L.oard_supported(C.byref(cfg)), "oard_supported (hidden_channels/num_radial not built)")
+            packed = dyn._get_packed(cfg, stream)
+            nfs = list(dyn.node_nfs)
+            if t_int is None:
+                t_int = torch.randint(1, ls.T + 1, size=(B,), device=dev).float()
+            t_int = t_int.detach().to(device=dev, dtype=torch.float32).reshape(B).contiguous()
+            counts = [int(m.numel()) for m in masks]
+            noise = self._noise_blocks(counts, nfs, draw, 2, dev)          # z_t's block, then z_0's
+            hm = [r["mask_host"] for r in reps] if have_host else masks
+            hs = [r["size_host"] for r in reps] if have_host else sizes
+            combined_mask, _, n_frag_switch = ls._layout(hm, hs, need_edges=False)
+            topo = dyn._get_train_topology(cfg, None, n_frag_switch, combined_mask, stream, device=dev)
+            gamma, snr = self._eval_tables(dev)
+            pos, one_hot, charge, nv, nb, sc = self._loss_operands(reps)
+            z_t, eps_t, z_0, eps_0 = ([torch.empty(counts[k], nfs[k], device=dev) for k in range(K)] for _ in range(4))
+            arr = _capi.ptr_array
+            pos_only = 1 if ls.pos_only else 0
+            _capi.check(L.oard_loss_eval_prepare(C.byref(cfg), topo.handle, arr(pos), arr(one_hot), arr(charge), arr(noise[0]), arr(noise[1]),
+                                                 t_int.data_ptr(), gamma.data_ptr(), ls.T, nv, nb, pos_only,
+                                                 sum(1 << int(k) for k in ls.fixed_idx), arr(z_t), arr(eps_t), arr(z_0), arr(eps_0), stream),
+                        "oard_loss_eval_prepare")
+            net_t = self._infer(dyn, cfg, topo, packed, z_t, (t_int / ls.T).view(B, 1), cond, stream)
+            net_0 = self._infer(dyn, cfg, topo, packed, z_0, torch.zeros(B, 1, device=dev), cond, stream)
+            nll = torch.empty(B, device=dev)
+            terms = torch.empty(5 * K + 2, B, device=dev)
+            delta_log_px = -((sum(counts) - 1) * ls.pos_dim) * math.log(ls.norm_values[0])      # loss.py:153, from the host sizes
+            _capi.check(L.oard_loss_eval_terms(C.byref(cfg), topo.handle, arr(eps_t), arr(net_t), arr(eps_0), arr(net_0), arr(z_0),
+                                               arr(one_hot), arr(charge), t_int.data_ptr(), gamma.data_ptr(), snr.data_ptr(), ls.T, nv, nb,
+                                               sc, pos_only, float(delta_log_px), B, nll.data_ptr(), terms.data_ptr(), stream),
+                        "oard_loss_eval_terms")
+        return nll, terms
+
+    def _eval_tables(self, dev) -> Tuple[Tensor, Tensor]:
+        """The gamma table and the SNR_weight table of `oard_loss_eval_terms` on the device, uploaded once."""
+        if self._gamma_dev is None or self._gamma_dev.device != dev:
+            self._gamma_dev = self.loss.schedule.gamma.to(device=dev, dtype=torch.float32).contiguous()
+        if self._snr_dev is None or self._snr_dev.device != dev:
+            self._snr_dev = vlb_snr_table(self.loss.schedule).to(dev)
+        return self._gamma_dev, self._snr_dev
+
+    @torch.no_grad()
+    def validation_step(self, batch, weights: str = "live", prefix: str = "val", rmsd: bool = False, **kw) -> Tensor:
+        """`DDPMModule.validation_step` (`_shared_eval`, pl_trainer.py:349-382) without a host read: -> the device row
+        [totloss, error_t_0 .., unorm_error_t_0 .., rmsd, rmsd-median], totloss = nll.mean() of `eval_loss(batch, weights, **kw)` and
+        the `info` means as pl_trainer.py:265-269 (error_t_k: the mean of the normalised, scaled error / (scales[k] + 1e-4)).
+        `rmsd=True` runs `eval_inpaint_batch(batch, weights=weights)` (that call reads the host); otherwise both RMSD entries are NaN,
+        as the reference logs on the epochs it does not sample.  The row and the per-reaction nll are remembered under `prefix` for
+        `validation_epoch_end`.  Same API on a trainer that cannot fuse (see `eval_loss`).  `kw`: t_int=, draw= (tests)."""
+        nll, terms = self.eval_loss(batch, weights=weights, **kw)
+        K = (int(terms.shape[0]) - 2) // 5
+        means = terms[: 2 * K].mean(dim=1)
+        div = self._val_div.get((means.device, means.dtype))
+        if div is None:
+            div = self._val_div[(means.device, means.dtype)] = torch.tensor(
+                [float(s) + 1e-4 for s in self.loss.scales[:K]] + [1.0] * K, dtype=means.dtype, device=means.device)
+        if rmsd:
+            tail = torch.tensor(self.eval_inpaint_batch(batch, weights=weights), dtype=means.dtype, device=means.device)
+        else:
+            tail = torch.full((2,), float("nan"), dtype=means.dtype, device=means.device)
+        row = torch.cat([nll.mean().reshape(1).to(means.dtype), means / div, tail])
+        kept = self._val_kept.setdefault(prefix, ([], []))
+        kept[0].append(row)
+        kept[1].append(nll)
+        return row
+
+    def test_step(self, batch, weights: str = "live", rmsd: bool = False, **kw) -> Tensor:
+        """`DDPMModule.test_step`: `validation_step` logged under the prefix `test`."""
+        return self.validation_step(batch, weights=weights, prefix="test", rmsd=rmsd, **kw)
+
+    def validation_epoch_end(self) -> Dict[str, float]:
+        """`DDPMModule.validation_epoch_end` (pl_trainer.py:376-382) over the `validation_step` / `test_step` calls since the last one, in
+        ONE host read: `<prefix>-<key>` for totloss, error_t_k, unorm_error_t_k, rmsd and rmsd-median, the mean over the batches that
+        gave a number (nanmean; the first-batch quirk of the reference's `average_over_batch_metrics` is not reproduced, as in
+        `ConfidenceTrainer.validation_epoch_end`), and `<prefix>-pooled-totloss`: the mean nll over ALL remembered reactions, which
+        differs from the mean of batch means when the batches are of unequal size.  With collectives on, the sums and counts go through
+        one small all-reduce first, so every rank returns the same dict (the reference's `sync_dist=True`); every rank then has to have
+        logged under the same prefixes.  Forgets the batches.  No step since the last call: an empty dict."""
+        if not self._val_kept:
+            return {}
+        prefixes = sorted(self._val_kept)
+        parts = []
+        for p in prefixes:
+            rows_list, nlls = self._val_kept[p]
+            rows = torch.stack(rows_list).double()
+            ok = ~torch.isnan(rows)
+            every = torch.cat(nlls).double()
+            parts += [torch.where(ok, rows, torch.zeros_like(rows)).sum(dim=0), ok.sum(dim=0).double(), every.sum().reshape(1),
+                      torch.full((1,), float(every.numel()), dtype=torch.float64, device=rows.device)]
+        width = int(parts[0].numel())
+        flat = torch.cat(parts)
+        if self.collectives:
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
+        per = 2 * width + 2
+        flat = flat.view(len(prefixes), per)
+        stats = torch.cat([flat[:, :width] / flat[:, width: 2 * width], flat[:, 2 * width: 2 * width + 1] / flat[:, 2 * width + 1:]],
+                          dim=1).tolist()                                      # the one host read
+        K = (width - 3) // 2
+        names = ["totloss"] + [f"error_t_{k}" for k in range(K)] + [f"unorm_error_t_{k}" for k in range(K)] + ["rmsd", "rmsd-median"]
+        out: Dict[str, float] = {}
+        for p, vals in zip(prefixes, stats):
+            out.update({f"{p}-{k}": v for k, v in zip(names, vals)})
+            out[f"{p}-pooled-totloss"] = vals[width]
+        self._val_kept = {}
+        return out
 
     # ---- the moving average of the weights (trainer/ema.py; see `ema_decay` in __init__) ---------------------------------------------------
     def _need_ema(self) -> Tensor:
@@ -474,6 +659,34 @@ class DDPMTrainer(FlatTrainerState):
             self.flat_grad.mul_(gscale)                # clip_grad_norm_: g *= max_norm / (norm + 1e-6)
         return grad_norm, max_grad_norm
 
+    # ---- what the fused step and the fused evaluation hand to the loss kernels --------------------------------------------------------
+    def _loss_operands(self, reps):
+        """-> (pos, one_hot, charge: contiguous float32 / int64 / int64 per object; norm_values[3], norm_biases[3], scales[K] as C arrays)."""
+        ls, K = self.loss, len(reps)
+        pos = [r["pos"].detach().to(torch.float32).contiguous() for r in reps]
+        one_hot = [r["one_hot"].detach().to(torch.int64).contiguous() for r in reps]
+        charge = [r["charge"].detach().to(torch.int64).contiguous() for r in reps]
+        f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])              # noqa: E731
+        return pos, one_hot, charge, f3(ls.norm_values), f3(ls.norm_biases), (C.c_float * K)(*[float(x) for x in ls.scales[:K]])
+
+    @staticmethod
+    def _noise_blocks(counts: List[int], nfs: List[int], draw, blocks: int, dev) -> List[List[Tensor]]:
+        """`blocks` sets of raw N(0,1) draws, each one [n_k, nf_k] tensor per object.  Injected draws (`draw`) follow DiffusionLoss's
+        protocol, block after block (per object: randn(n, 3) then randn(n, nf - 3)); the default is ONE device randn for all of it,
+        viewed per block and object (same distribution, one launch)."""
+        if draw is not None:
+            return [[torch.cat([draw((c, 3)).float(), draw((c, f - 3)).float()], dim=1).contiguous() for c, f in zip(counts, nfs)]
+                    for _ in range(blocks)]
+        flat = torch.randn(blocks * sum(c * f for c, f in zip(counts, nfs)), device=dev)
+        out, off = [], 0
+        for _ in range(blocks):
+            block = []
+            for c, f in zip(counts, nfs):
+                block.append(flat[off: off + c * f].view(c, f))
+                off += c * f
+            out.append(block)
+        return out
+
     # ---- fused step (HIP module): no autograd graph, ~20 launches around the network call ----------------------------------------
     def _fused_part(self, cfg, packed, reps, cond, t_int: Tensor, noise: List[Tensor], counts: List[int], host_masks, host_sizes,
                     terms: Tensor, col0: int, buffers: Optional[_CallBuffers] = None):
@@ -496,15 +709,10 @@ class DDPMTrainer(FlatTrainerState):
         gamma = self._gamma_dev
         if gamma is None or gamma.device != dev:
             gamma = self._gamma_dev = ls.schedule.gamma.to(device=dev, dtype=torch.float32).contiguous()
-        pos = [r["pos"].detach().to(torch.float32).contiguous() for r in reps]
-        one_hot = [r["one_hot"].detach().to(torch.int64).contiguous() for r in reps]
-        charge = [r["charge"].detach().to(torch.int64).contiguous() for r in reps]
+        pos, one_hot, charge, nv, nb, sc = self._loss_operands(reps)
         z = [torch.empty(counts[k], nfs[k], device=dev) for k in range(K)]
         eps = [torch.empty_like(x) for x in z]
         arr = _capi.ptr_array
-        f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])              # noqa: E731
-        nv, nb = f3(ls.norm_values), f3(ls.norm_biases)
-        sc = (C.c_float * K)(*[float(x) for x in ls.scales[:K]])
         fixed_mask = sum(1 << int(k) for k in ls.fixed_idx)
         _capi.check(L.oard_loss_prepare(C.byref(cfg), topo.handle, arr(pos), arr(one_hot), arr(charge), arr(noise), t_int.data_ptr(),
                                         gamma.data_ptr(), ls.T, nv, nb, 1 if ls.pos_only else 0, fixed_mask, arr(z), arr(eps), stream),
@@ -557,14 +765,7 @@ class DDPMTrainer(FlatTrainerState):
                 t_int = torch.randint(0, ls.T + 1, size=(B, 1), device=dev).float()
             t_int = t_int.detach().to(device=dev, dtype=torch.float32).reshape(B).contiguous()
             counts = [int(m.numel()) for m in masks]
-            if draw is None:                          # ONE draw for the whole step's noise, viewed per object ([n_k, nf_k] blocks)
-                flat = torch.randn(sum(c * f for c, f in zip(counts, nfs)), device=dev)
-                noise, off = [], 0
-                for c, f in zip(counts, nfs):
-                    noise.append(flat[off: off + c * f].view(c, f))
-                    off += c * f
-            else:                                     # injected draws follow DiffusionLoss's protocol: (n, 3) then (n, nf - 3) per object
-                noise = [torch.cat([draw((c, 3)).float(), draw((c, f - 3)).float()], dim=1).contiguous() for c, f in zip(counts, nfs)]
+            noise = self._noise_blocks(counts, nfs, draw, 1, dev)[0]
             dests = {id(p): p.grad for p in self.params}
             terms = torch.empty(2 * K, B, device=dev)
             if self.microbatches == 2 and have_host and B >= 2:
