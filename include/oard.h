@@ -650,6 +650,50 @@ int oard_rank_metrics(const float* score_dev, const float* target_dev, int64_t n
                       double* rank_score_dev /* [n] or NULL */, double* rank_target_dev /* [n] or NULL */,
                       double* out_dev /* [n_segments, 8] or NULL */, oard_stream_t stream);
 
+/* ---- reaction dataset: one gather launch per batch (csrc/oard_dataset.h) --------------------------------------------------------
+ * Replaces: ProcessedTS1x.__getitem__ + BaseDataset.collate_fn (oa_reactdiff/dataset/base_dataset.py:51-88) over what
+ * ProcessedTS1x.__init__ builds per sample (dataset/transition1x.py:21-150, base_dataset.py:142-217).
+ *
+ * oard_reaction_store is a plain description of arrays the caller owns: no handle, no hidden state.  Per SOURCE object (0 reactant,
+ * 1 transition state, 2 product): offsets [n_raw + 1] (exclusive prefix sums of the atom counts), raw float32 positions [sum n, 3], atomic
+ * numbers [sum n] (1, 6, 7, 8 or 9: the caller checks).  sel [n_sel]: the selected raw reactions.  A virtual sample index v in
+ * [0, n_sel * (1 + swap) * (1 + reflect)) decodes as  f_bit = v / (n_sel * s), j = v % (n_sel * s), s_bit = j / n_sel, r = sel[j % n_sel]
+ * (original block, swapped block, then the reflected copy of both).  Output object k reads source src_obj[k]; a swapped sample reads
+ * source 2 - src_obj[k].  A reflected sample negates the last raw coordinate of every object with reflect_obj[k].  center: positions
+ * minus their mean over the molecule (float64 sum in a fixed order, one rounding).  zero_charge: the charge column is 0.  append_frag:
+ * charge has a second column holding append_charge[k].  target / rmsd (or NULL): [n_raw] columns read at v % n_raw, the reference's
+ * unselected lists.  ediff[0] / ediff[1] (or NULL): [n_raw] columns of the named object and of its swap partner, read at r.
+ *
+ * oard_dataset_gather writes samples index_dev[first .. first + B) into the outputs: per output object k  size [B], pos [n_k, 3],
+ * one_hot [n_k, 5], charge [n_k, 1 + append_frag], mask [n_k] (= b), where sample b starts at row
+ * epoch_off_dev[k][first + b] - epoch_off_dev[k][first]  (epoch_off_dev[k]: exclusive prefix sums of object k's atom counts along
+ * index_dev, one entry more than index_dev); condition [B] = 0; target / rmsd / ediff [B] where the store has the column (the output is
+ * required exactly then).  The pointer ARRAYS are host arrays of n_obj device pointers.  OARD_EINVAL - before any HIP call - for a NULL
+ * store, array or entry, n_obj not 1 or 3, a src_obj outside 0..2, a flag outside {0, 1}, n_raw / n_sel < 1, n_sel > n_raw, first < 0, B < 0,
+ * (first + B) or B * n_obj >= 2^31, a column / output mismatch.  B == 0 returns OARD_OK without a launch.  One launch, no allocation,
+ * no copy; asynchronous on `stream`, capturable.  No counterpart kernel in the reference. */
+#define OARD_STORE_OBJECTS 3
+typedef struct oard_reaction_store {
+    const int64_t* offsets[OARD_STORE_OBJECTS];
+    const float* pos[OARD_STORE_OBJECTS];
+    const int32_t* z[OARD_STORE_OBJECTS];
+    const int64_t* sel;
+    const int64_t* target;
+    const float* rmsd;
+    const float* ediff[2];
+    int64_t n_raw, n_sel;
+    int32_t n_obj;
+    int32_t src_obj[OARD_STORE_OBJECTS];
+    int32_t reflect_obj[OARD_STORE_OBJECTS];
+    int32_t append_charge[OARD_STORE_OBJECTS];
+    int32_t swap, reflect, center, zero_charge, append_frag;
+} oard_reaction_store;
+int oard_dataset_gather(const oard_reaction_store* store, const int64_t* index_dev, const int64_t* const* epoch_off_dev,
+                        int64_t first, int64_t B,
+                        int64_t* const* size_dev, float* const* pos_dev, int64_t* const* one_hot_dev, int64_t* const* charge_dev,
+                        int64_t* const* mask_dev, int64_t* condition_dev, int64_t* target_dev /* or NULL */,
+                        float* rmsd_dev /* or NULL */, float* ediff_dev /* or NULL */, oard_stream_t stream);
+
 /* The library's own streams of the current device(three non-blocking streams, chosen once per device so that each runs on a hardware
  * queue of its own beside the caller's stream - the runtime serves a process's streams from 4 queues): 0 = the training sweep's
  * gradient stream (and the second sub-batch of a multi-part forward), 1 = the third sub-batch, 2 = topology uploads (and the fourth).

@@ -3,6 +3,7 @@
     from oareactdiff_amd import EGNNDynamics        # drop-in for oa_reactdiff.dynamics.EGNNDynamics(model=LEFTNet)
     from oareactdiff_amd import Confidence          # drop-in for oa_reactdiff.dynamics.confidence.Confidence(model=LEFTNet)
     from oareactdiff_amd import ConfidenceTrainer   # ConfModule's training step for Confidence(..., trainable=True)
+    from oareactdiff_amd import ReactionStore, DeviceLoader   # ProcessedTS1x + DataLoader on the device, one launch per batch
 
 See DESIGN.md (path, kernels, measurement) and INTEGRATION.md (binding)."""
 from .dynamics import EGNNDynamics  # noqa: F401
@@ -12,6 +13,7 @@ from .sampler import DiffusionSampler  # noqa: F401
 from .loss import DiffusionLoss  # noqa: F401
 from .trainer import DDPMTrainer  # noqa: F401
 from .conf_trainer import ConfidenceTrainer  # noqa: F401
+from .data import DeviceLoader, ReactionStore  # noqa: F401
 from .graph_tools import get_edges_index, get_mask_for_frag, get_n_frag_switch, get_subgraph_mask  # noqa: F401
 
-__all__ = ["EGNNDynamics", "Confidence", "rank_candidates", "ranking_report", "midrank", "rank_metrics", "binary_auroc", "pearson_corrcoef", "spearman_corrcoef", "DiffusionSampler", "DiffusionLoss", "DDPMTrainer", "ConfidenceTrainer", "get_edges_index", "get_mask_for_frag", "get_n_frag_switch", "get_subgraph_mask"]
+__all__ = ["EGNNDynamics", "Confidence", "rank_candidates", "ranking_report", "midrank", "rank_metrics", "binary_auroc", "pearson_corrcoef", "spearman_corrcoef", "DiffusionSampler", "DiffusionLoss", "DDPMTrainer", "ConfidenceTrainer", "ReactionStore", "DeviceLoader", "get_edges_index", "get_mask_for_frag", "get_n_frag_switch", "get_subgraph_mask"]

@@ -8,7 +8,7 @@ import os
 from .build import LIB
 
 OARD_MAX_OBJECTS = 8
-ABI_VERSION = 2047            # OARD_VERSION of csrc/oard_hip.hip (checked by lib(): a stale library is refused, not misread)
+ABI_VERSION = 2048            # OARD_VERSION of csrc/oard_hip.hip (checked by lib(): a stale library is refused, not misread)
 OARD_OK, OARD_EINVAL, OARD_ENOTCOMPLETE, OARD_EHIP, OARD_ENOMEM = 0, -1, -2, -3, -4
 ERRORS = {OARD_EINVAL: "invalid argument / unsupported configuration", OARD_ENOTCOMPLETE: "topology is not complete-per-sample",
           OARD_EHIP: "HIP runtime error", OARD_ENOMEM: "workspace too small"}
@@ -30,7 +30,7 @@ EXPORTS = ["oard_version", "oard_supported", "oard_param_count", "oard_packed_by
            "oard_adamw_step_ema", "oard_adamw_step_dev_ema", "oard_ema_update", "oard_kabsch_rmsd", "oard_matched_rmsd", "oard_rank_metrics",
            "oard_graph_create", "oard_graph_destroy", "oard_graph_num_nodes", "oard_graph_num_edges", "oard_graph_object_rows",
            "oard_graph_is_complete", "oard_graph_workspace_bytes", "oard_graph_forward", "oard_library_stream",
-           "oard_confidence_forward", "oard_confidence_forward_train", "oard_confidence_tail_backward"]
+           "oard_confidence_forward", "oard_confidence_forward_train", "oard_confidence_tail_backward", "oard_dataset_gather"]
 STAGE_RECOMPUTE, STAGE_UPDATE, STAGE_MESSAGE, STAGE_GCL_NODE, STAGE_NODE_PRE, STAGE_GCL_EDGE, STAGE_EQUI_EDGE = range(7)
 SCRATCH_XH, SCRATCH_XQ, SCRATCH_CR, SCRATCH_DCD, SCRATCH_DCR = range(1, 6)
 
@@ -47,6 +47,21 @@ class OardConfig(C.Structure):
         ("n_obj", C.c_int32), ("node_nf", C.c_int32 * OARD_MAX_OBJECTS), ("enc_alias", C.c_int32 * OARD_MAX_OBJECTS),
         ("condition_nf", C.c_int32), ("condition_time", C.c_int32), ("pos_dim", C.c_int32), ("cutoff", C.c_float),
         ("reflect_equiv", C.c_int32), ("precision", C.c_int32),
+    ]
+
+
+OARD_STORE_OBJECTS = 3
+
+
+class OardReactionStore(C.Structure):
+    """`oard_reaction_store` (include/oard.h): device pointers, counts and flags of a reaction store; no handle behind it."""
+    _fields_ = [
+        ("offsets", C.c_void_p * OARD_STORE_OBJECTS), ("pos", C.c_void_p * OARD_STORE_OBJECTS), ("z", C.c_void_p * OARD_STORE_OBJECTS),
+        ("sel", C.c_void_p), ("target", C.c_void_p), ("rmsd", C.c_void_p), ("ediff", C.c_void_p * 2),
+        ("n_raw", C.c_int64), ("n_sel", C.c_int64), ("n_obj", C.c_int32),
+        ("src_obj", C.c_int32 * OARD_STORE_OBJECTS), ("reflect_obj", C.c_int32 * OARD_STORE_OBJECTS),
+        ("append_charge", C.c_int32 * OARD_STORE_OBJECTS),
+        ("swap", C.c_int32), ("reflect", C.c_int32), ("center", C.c_int32), ("zero_charge", C.c_int32), ("append_frag", C.c_int32),
     ]
 
 
@@ -167,6 +182,8 @@ def lib() -> C.CDLL:
     L.oard_kabsch_rmsd.argtypes = [vp, i64, vp, i64, vp, i64, ci, cf, vp, vp, vp, vp]; L.oard_kabsch_rmsd.restype = ci
     L.oard_matched_rmsd.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, ci, cf, ci, vp, vp, vp, vp, vp, vp]; L.oard_matched_rmsd.restype = ci
     L.oard_rank_metrics.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]; L.oard_rank_metrics.restype = ci
+    L.oard_dataset_gather.argtypes = [C.POINTER(OardReactionStore), vp, pvp, i64, i64, pvp, pvp, pvp, pvp, pvp, vp, vp, vp, vp, vp]
+    L.oard_dataset_gather.restype = ci
     L.oard_library_stream.argtypes = [ci, pvp]; L.oard_library_stream.restype = ci
     # general edge lists (csrc/oard_general.hip)
     L.oard_graph_create.argtypes = [cfgp, vp, vp, i64, vp, i64, pvp]; L.oard_graph_create.restype = ci

@@ -29,7 +29,7 @@
 #include "oard_plan.h"        // the launch plan: every shape decision of the forward, host only
 #include "oard_inst.h"        // the heavy kernel families are instantiated in their own translation units: `extern template` here
 
-#define OARD_VERSION 2047      // + oard_loss_eval_prepare, oard_loss_eval_terms (2046: oard_rank_metrics; 2045: oard_matched_rmsd; 2044: oard_confidence_forward_train, oard_confidence_tail_backward; 2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
+#define OARD_VERSION 2048      // + oard_dataset_gather (2047: oard_loss_eval_prepare, oard_loss_eval_terms; 2046: oard_rank_metrics; 2045: oard_matched_rmsd; 2044: oard_confidence_forward_train, oard_confidence_tail_backward; 2043: oard_confidence_forward; 2042: oard_kabsch_rmsd; 2041: oard_adamw_step_ema, oard_adamw_step_dev_ema, oard_ema_update; 2040: oard_graph_*, oard_library_stream)
 // The first-generation kernels (weights straight from L2, one wave per 16 nodes: gcl_variant / equi_variant / node_variant 0) are the
 // A/B baseline of round 1 and a cross-check in tests/test_hip_parity.py::test_every_kernel_variant_is_parity_green; they are compiled
 // into experiment builds (-DOARD_EXPERIMENTS) only - a product library refuses those variants (oard_debug_option returns OARD_EINVAL).
@@ -832,7 +832,8 @@ static int equi_msg_backward_impl(const oard_config* c, const TopoDev& tp, const
 // plan of the weight-gradient GEMM: a pure function of the shape, so that the summation order (and with it the result,
 // bit for bit) does not depend on anything else.  Q (16-wide tiles, no padding waste) is the narrower operand; when that is
 // dY the kernel produces the transposed product.
-struct WgradPlan { int transposed, NT, nPB, nQG, PP, QP, gy; long long rpc; int n_chunks; int lds, PBW, QGW; };
+struct WgradPlan { int transposed, NT, nPB, nQG, PP, QP, gy; long long rpc; int n_chunks; int lds, PBW, QGW;
+                   long long cap; };      // cap: the chunk count asked for before rpc is rounded up (n_chunks <= cap; monotone in rows)
 // workgroup shapes of the LDS-panel kernel: NT tiles per Q group, PBW P blocks x QGW Q groups = the 8 tasks of a workgroup
 struct WglShape { int NT, PBW, QGW; };
 static const WglShape kWglShapes[2] = {{7, 4, 2}, {8, 4, 2}};
@@ -849,6 +850,7 @@ static WgradPlan wgrad_plan(int ncY, int ncX, long long rows) {
     want = std::min(want, std::max<long long>(1, cdiv(rows, rows < 16384 ? 128 : 64)));      // short contractions: fewer, longer chunks (the partials dominate)
     p.rpc = align_up((size_t)cdiv(std::max<long long>(rows, 1), want), 4 * OARD_WG_PD);
     p.n_chunks = (int)cdiv(std::max<long long>(rows, 1), p.rpc);
+    p.cap = want;
     // long contractions with at least two Q groups: the LDS-panel kernel (k_wgrad_lds), one 8-wave workgroup per CU and round; a
     // workgroup owns PBW P blocks x QGW Q groups of a row chunk.  Of the shapes that fill >= 85 % of their wave slots with tasks the
     // one that executes the fewest padded columns (P slots x 64) x (Q slots x 16 NT) is taken: 684 x 196 -> NT 7 (768 x 224);
@@ -876,6 +878,7 @@ static WgradPlan wgrad_plan(int ncY, int ncX, long long rows) {
         w2 = std::min(w2, std::max<long long>(1, cdiv(rows, 4 * WGL_ROWS)));
         p.rpc = align_up((size_t)cdiv(rows, w2), WGL_ROWS);
         p.n_chunks = (int)cdiv(rows, p.rpc);
+        p.cap = w2;
         p.gy = (int)tiles;
     }
     return p;
@@ -1998,14 +2001,31 @@ static int wgt_ones_col(int ncX, int i_len, int i_pad, int MI) {
     return MI < ncX ? MI : -1;                                     // i_pad == i_len: unsectioned, the first column behind the features
 }
 
+// The partials of a product with `rows` rows, bounded from above so that the bound never DECREASES with rows: a buffer sized for r rows
+// then holds every product of the same widths with fewer rows (the training scratch is sized from N, E + 1, A + 1 and serves calls with
+// E, A and per-object row counts).  The exact need is not monotone - a chunk's rows are rounded up, so one row more can mean one chunk
+// less, and the plan changes kernels at 16384 rows - and a batch whose edge count sat just below such a drop failed its step with
+// OARD_ENOMEM.  Bound: the chunk count asked for before the rounding (WgradPlan::cap; for the 16 x 16-tile kernel the largest over its
+// candidate tilings), and from 16384 rows on also the bound of 16383.
+static size_t wgrad_partials_bound(int ncY, int ncX, int64_t rows) {
+    const WgradPlan p = wgrad_plan(ncY, ncX, rows);
+    size_t big = ((size_t)p.cap * p.PP * p.QP + (size_t)p.cap * std::max(p.PP, p.QP)) * sizeof(float);
+    if (g_wgrad_t16 > 0 && rows >= 16384 && !(ncY & 15) && !(ncX & 15)) {
+        const int tY = ncY / 16, tX = ncX / 16, MT = std::max(tY, tX), NT = std::min(tY, tX);     // either orientation: the same tile count
+        for (int nPT = (int)cdiv(MT, WGT_PT); nPT <= (int)cdiv(MT, WGT_PT) + 1; ++nPT)
+            for (int nQT = (int)cdiv(NT, WGT_QT); nQT <= (int)cdiv(NT, WGT_QT) + 2; ++nQT) {
+                long long nch = std::max<long long>(8, (long long)g_wgrad_t16 / (nPT * nQT) / 8 * 8);
+                nch = std::min(nch, std::max<long long>(1, cdiv(rows, 4 * WGT_R)));
+                big = std::max(big, (size_t)nch * tY * tX * 256 * sizeof(float));
+            }
+    }
+    return big;
+}
+
 size_t oard_wgrad_scratch_bytes(int ncY, int ncX, int64_t rows) {
     if (ncY < 4 || ncX < 4 || rows < 0) return 0;
-    const WgradPlan p = wgrad_plan(ncY, ncX, rows);
-    size_t big = ((size_t)p.n_chunks * p.PP * p.QP + (size_t)p.n_chunks * std::max(p.PP, p.QP)) * sizeof(float);
-    for (int silu = 0; silu < 2; ++silu) {
-        const WgtPlan t = wgt_plan(ncY, ncX, rows, silu);
-        if (t.ok) big = std::max(big, (size_t)t.n_chunks * t.MT * t.NT * 256 * sizeof(float));
-    }
+    size_t big = wgrad_partials_bound(ncY, ncX, rows);
+    if (rows >= 16384) big = std::max(big, wgrad_partials_bound(ncY, ncX, 16383));
     return std::max(big, (size_t)1024 * 1024 * sizeof(float));        // the small-output path: <= 1024 chunks x <= 1024 outputs
 }
 
@@ -2219,6 +2239,7 @@ int oard_wgrad(const float* dY, int ldY, int ncY, int o_len, int o_pad, int MO, 
 #include "oard_kabsch.h"     // k_kabsch_rmsd: the validation metric (oard_kabsch_rmsd)
 #include "oard_match.h"      // k_matched_rmsd: the same with the atoms matched first (oard_matched_rmsd)
 #include "oard_rank.h"       // k_rank_count, k_rank_stats: midranks per segment, AUROC / Pearson / Spearman (oard_rank_metrics)
+#include "oard_dataset.h"    // k_reaction_gather: a batch from the device-resident reaction store in one launch (oard_dataset_gather)
 extern "C" {
 
 // ---- the backward sweep through the C ABI (include/oard.h) ------------------------------------------------------------------------
@@ -2585,6 +2606,34 @@ int oard_rank_metrics(const float* score, const float* target, int64_t n, const 
                (const double*)rank_target, out);
         HIP_TRY(hipGetLastError());
     }
+    return OARD_OK;
+}
+
+// ---- a batch from the device-resident reaction store (dataset/base_dataset.py:51-88, transition1x.py:21-150; oard_dataset.h) -----------------
+int oard_dataset_gather(const oard_reaction_store* s, const int64_t* index, const int64_t* const* epoch_off, int64_t first, int64_t B,
+                        int64_t* const* size, float* const* pos, int64_t* const* one_hot, int64_t* const* charge, int64_t* const* mask,
+                        int64_t* condition, int64_t* target, float* rmsd, float* ediff, oard_stream_t stream) {
+    if (!s || !index || !epoch_off || !size || !pos || !one_hot || !charge || !mask || !condition) return OARD_EINVAL;
+    if ((s->n_obj != 1 && s->n_obj != OARD_STORE_OBJECTS) || s->n_raw < 1 || s->n_sel < 1 || !s->sel) return OARD_EINVAL;
+    if (first < 0 || B < 0 || first >= 0x7fffffffLL || B >= 0x7fffffffLL || first + B >= 0x7fffffffLL || B * s->n_obj >= 0x7fffffffLL) return OARD_EINVAL;
+    for (int flag : {s->swap, s->reflect, s->center, s->zero_charge, s->append_frag}) if (flag != 0 && flag != 1) return OARD_EINVAL;
+    if (s->n_sel > s->n_raw) return OARD_EINVAL;                      // sel is a subset of the raw reactions
+    if ((target != nullptr) != (s->target != nullptr) || (rmsd != nullptr) != (s->rmsd != nullptr)) return OARD_EINVAL;
+    if ((ediff != nullptr) != (s->ediff[0] != nullptr) || (s->ediff[0] != nullptr) != (s->ediff[1] != nullptr)) return OARD_EINVAL;
+    DatasetOut o = {};
+    for (int k = 0; k < s->n_obj; ++k) {
+        const int src = s->src_obj[k];
+        if (src < 0 || src >= OARD_STORE_OBJECTS || (s->reflect_obj[k] != 0 && s->reflect_obj[k] != 1)) return OARD_EINVAL;
+        for (int q : {src, s->swap ? 2 - src : src}) if (!s->offsets[q] || !s->pos[q] || !s->z[q]) return OARD_EINVAL;
+        if (!epoch_off[k] || !size[k] || !pos[k] || !one_hot[k] || !charge[k] || !mask[k]) return OARD_EINVAL;
+        o.size[k] = (long long*)size[k]; o.pos[k] = pos[k]; o.one_hot[k] = (long long*)one_hot[k]; o.charge[k] = (long long*)charge[k];
+        o.mask[k] = (long long*)mask[k]; o.epoch_off[k] = (const long long*)epoch_off[k];
+    }
+    o.condition = (long long*)condition; o.target = (long long*)target; o.rmsd = rmsd; o.ediff = ediff;
+    if (B == 0) return OARD_OK;
+    LAUNCH(F_OTHER, k_reaction_gather, cdiv(B * s->n_obj, DATASET_WAVES), DATASET_WAVES * 64, (hipStream_t)stream, *s, (const long long*)index,
+           (long long)first, (long long)B, o);
+    HIP_TRY(hipGetLastError());
     return OARD_OK;
 }
 

@@ -241,7 +241,8 @@ class DDPMTrainer(FlatTrainerState):
         """A host batch (the dataset's collate output: per object {size, pos, one_hot, charge, mask}, conditions) moved to `device`
         with the HOST copies of `mask` / `size` kept beside the device tensors (`mask_host`, `size_host`): the fused step builds the
         batch layout from them, so a never-seen layout - every step of a real training run - costs no device -> host copy.  Batches
-        without the host copies work as before (one blocking copy of the masks per new layout)."""
+        without the host copies work as before (one blocking copy of the masks per new layout).  `data.DeviceLoader` yields batches in
+        this layout straight from a device-resident dataset, host copies included: they need no `to_device`."""
         reps, cond = batch
         out = []
         for r in reps:
