@@ -267,6 +267,8 @@ class EGNNDynamics(nn.Module):
         H, R, L, Cc = self._dims
         cfg = _capi.OardConfig()
         cfg.hidden, cfg.num_radial, cfg.num_layers, cfg.in_hidden = H, R, L, Cc
+        if len(self.node_nfs) > _capi.OARD_MAX_OBJECTS:
+            raise _capi.OardError(f"{len(self.node_nfs)} objects per reaction: the library takes at most {_capi.OARD_MAX_OBJECTS} (OARD_MAX_OBJECTS)")
         cfg.n_obj = len(self.node_nfs)
         for k, nf in enumerate(self.node_nfs):
             cfg.node_nf[k] = nf

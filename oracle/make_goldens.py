@@ -113,15 +113,16 @@ def run_case(case: dict) -> None:
     name = case["name"]
     cfg = dict(case["model_config"])
     node_nfs, cnf = case["node_nfs"], case["condition_nf"]
+    ctime = bool(case.get("condition_time", True))
     xh, edge_index, t, conditions, n_frag_switch, combined_mask = make_inputs(case)
 
-    spec = state_spec(cfg, node_nfs, cnf)
+    spec = state_spec(cfg, node_nfs, cnf, condition_time=ctime)
     sd32 = synthetic_state_dict(spec, cfg, seed=42, dtype=torch.float32)
 
     torch.set_default_dtype(torch.float32)
     ref = EGNNDynamics(model_config=dict(cfg), fragment_names=[f"o{k}" for k in range(len(node_nfs))],
                        node_nfs=node_nfs, edge_nf=0, condition_nf=cnf, model=LEFTNet,
-                       device=torch.device("cpu"))
+                       condition_time=ctime, device=torch.device("cpu"))
     ref.load_state_dict(sd32, strict=True)                      # pins names and shapes
     ref.eval()
     with torch.no_grad():
@@ -133,7 +134,7 @@ def run_case(case: dict) -> None:
     torch.set_default_dtype(torch.float64)
     ref64 = EGNNDynamics(model_config=dict(cfg), fragment_names=[f"o{k}" for k in range(len(node_nfs))],
                          node_nfs=node_nfs, edge_nf=0, condition_nf=cnf, model=LEFTNet,
-                         device=torch.device("cpu"))
+                         condition_time=ctime, device=torch.device("cpu"))
     sd64 = {k: v.double() for k, v in sd32.items()}
     ref64.load_state_dict(sd64, strict=True)
     ref64.eval()
@@ -144,17 +145,18 @@ def run_case(case: dict) -> None:
     # oracle, float64
     st_lit, st_ex = {}, {}
     o_lit = oracle.dynamics_forward(sd64, cfg, xh64, edge_index, t.double(), conditions.double(),
-                                    n_frag_switch, combined_mask, cnf, nodeframe="literal",
-                                    stages=st_lit, direct_vel=False)
+                                    n_frag_switch, combined_mask, cnf, condition_time=ctime,
+                                    nodeframe="literal", stages=st_lit, direct_vel=False)
     # (the exact-arithmetic node frame is a property of the COMPLETE graph per sample: the general-edge-list cases keep the literal frame)
     nf_hip = "literal" if case.get("edges") else "exact"
     o_ex = oracle.dynamics_forward(sd64, cfg, xh64, edge_index, t.double(), conditions.double(),
-                                   n_frag_switch, combined_mask, cnf, nodeframe=nf_hip, stages=st_ex)
+                                   n_frag_switch, combined_mask, cnf, condition_time=ctime, nodeframe=nf_hip,
+                                   stages=st_ex)
     torch.set_default_dtype(torch.float32)
     # oracle, float32 network on float64 geometry, exact node frame: the arithmetic model of
     # the HIP path, in plain torch
     o_ex32 = oracle.dynamics_forward(sd32, cfg, xh, edge_index, t, conditions, n_frag_switch,
-                                     combined_mask, cnf, nodeframe=nf_hip, geom64=True)
+                                     combined_mask, cnf, condition_time=ctime, nodeframe=nf_hip, geom64=True)
 
     nz = [k for k in range(len(xh)) if xh[k].size(0)]
     pd = 3
@@ -195,6 +197,7 @@ def run_case(case: dict) -> None:
     for key in case.get("stages", ["labels", "edge_mask", "pos_frame", "s0", "pos_prjt", "dpos", "h_out"]):
         arrays["stage." + key] = st_lit[key].numpy()
     meta = dict(case)
+    meta["condition_time"] = ctime
     meta["report"] = report
     meta["weights"] = {"generator": "oareactdiff_amd.spec.synthetic_state_dict", "seed": 42}
     arrays["meta"] = np.array(json.dumps(meta))
@@ -250,6 +253,22 @@ CASES = [
          fragments_nodes=[[3, 2, 4], [2, 0, 3], [1, 3, 2]], t_1d=False, pos_scale=1.5, onehot=True, edges="arbitrary", n_edges=80),
     dict(name="g11_components_noreflect", model_config=dict(TEST_CFG, num_layers=2, reflect_equiv=False), node_nfs=[9, 9, 9],
          condition_nf=1, fragments_nodes=[[6, 4]] * 3, t_1d=False, onehot=True, edges="components"),
+    # G13: object counts other than three (the library takes 1 to 8, OARD_MAX_OBJECTS) and the wrapper's width limits.  One object: every
+    # edge is an inner edge (one sample is a single atom without any edge); two objects without conditions, 1-D t, one empty group; four
+    # objects whose embedding (10) + t + 5 conditions fill all 16 columns of in_hidden_channels = 16, feature widths 1 and 16 side by
+    # side; eight objects; and three objects without the time column (condition_time = False).  The reference cannot run without BOTH
+    # the time column and conditions (egnn_dynamics.py:145 slices `h_final[:, :-condition_dim]`, which is empty at condition_dim = 0),
+    # so g13_no_time keeps one condition column; tests/test_object_counts.py runs the both-off configuration against the oracle alone.
+    dict(name="g13_one_object", model_config=dict(TEST_CFG, num_layers=2), node_nfs=[9], condition_nf=1,
+         fragments_nodes=[[5, 3, 1]], t_1d=False),
+    dict(name="g13_two_objects_nocond", model_config=dict(TEST_CFG, num_layers=2), node_nfs=[7, 12], condition_nf=0,
+         fragments_nodes=[[4, 0, 2], [3, 5, 1]], t_1d=True),
+    dict(name="g13_four_objects_wide", model_config=dict(TEST_CFG, num_layers=2, in_hidden_channels=16), node_nfs=[4, 19, 9, 6],
+         condition_nf=5, fragments_nodes=[[2, 3], [1, 4], [3, 0], [2, 2]], t_1d=False),
+    dict(name="g13_eight_objects", model_config=dict(TEST_CFG, num_layers=2), node_nfs=[9] * 8, condition_nf=1,
+         fragments_nodes=[[2, 1]] * 8, t_1d=False),
+    dict(name="g13_no_time", model_config=dict(TEST_CFG, num_layers=2), node_nfs=[9, 9, 9], condition_nf=1,
+         fragments_nodes=[[4, 2], [3, 5], [2, 3]], t_1d=False, condition_time=False),
 ]
 
 if __name__ == "__main__":

@@ -11,7 +11,9 @@ from oareactdiff_amd.spec import state_spec, synthetic_state_dict
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ALL_CASES = ["g1_wrapper_small", "g2_prod_b2_n23", "g2s_prod_b1_n5", "g3_cutoff_ragged",
              "g3p_prod_cutoff", "g6_h32_r32",
-             "g10_noreflect_h32", "g10p_noreflect_prod"]      # reflect_equiv = False (leftnet.py:268-272, 794-796)
+             "g10_noreflect_h32", "g10p_noreflect_prod",      # reflect_equiv = False (leftnet.py:268-272, 794-796)
+             # 1, 2, 4 and 8 objects (one object: every edge is an inner edge; 16 of 16 h_in columns in use at four); no time column
+             "g13_one_object", "g13_two_objects_nocond", "g13_four_objects_wide", "g13_eight_objects", "g13_no_time"]
 
 
 def rel(a, b):
@@ -32,6 +34,7 @@ class Case:
         self.cfg = dict(self.meta["model_config"])
         self.node_nfs = self.meta["node_nfs"]
         self.cnf = self.meta["condition_nf"]
+        self.condition_time = bool(self.meta.get("condition_time", True))
         self.n_obj = len(self.node_nfs)
         self.xh = [torch.from_numpy(z[f"xh{k}"]) for k in range(self.n_obj)]
         self.edge_index = torch.from_numpy(z["edge_index"])
@@ -41,7 +44,7 @@ class Case:
         self.combined_mask = torch.from_numpy(z["combined_mask"])
         self.ref64 = [torch.from_numpy(z[f"ref64_out{k}"]) for k in range(self.n_obj)]
         self.ref32 = [torch.from_numpy(z[f"ref32_out{k}"]) for k in range(self.n_obj)]
-        self.spec = state_spec(self.cfg, self.node_nfs, self.cnf)
+        self.spec = state_spec(self.cfg, self.node_nfs, self.cnf, condition_time=self.condition_time)
 
     def state_dict(self, dtype=torch.float32):
         return synthetic_state_dict(self.spec, self.cfg, seed=42, dtype=dtype)

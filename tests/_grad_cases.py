@@ -123,7 +123,8 @@ class GradCase:
 # Training steps off the fixtures: generated from a spec, references evaluated by the oracle on the CPU
 # =====================================================================================================================
 class GradSpec(NamedTuple):
-    """natm[k][b]: atoms of object k (R, TS, P) in reaction b.  t_int None, or a None entry: drawn from the case's generator."""
+    """natm[k][b]: atoms of object k (R, TS, P; any number of objects from 1 to 8) in reaction b.  t_int None, or a None entry: drawn
+    from the case's generator.  node_nfs None: 9 per object (the loss reads five one-hot columns and a charge)."""
     name: str
     natm: Tuple[Tuple[int, ...], ...]
     t_int: Optional[Tuple[Optional[int], ...]]
@@ -135,6 +136,8 @@ class GradSpec(NamedTuple):
     seed: int
     nea: Tuple[int, int, int]                  # (N, E, A) of the topology: nodes, edges, inner (same-object) edges
     reflect_equiv: bool = True
+    node_nfs: Optional[Tuple[int, ...]] = None
+    condition_nf: int = CNF
 
 
 _E64 = ((7, 4, 17), (16, 12, 11), (3, 3, 4))
@@ -142,7 +145,10 @@ _E64 = ((7, 4, 17), (16, 12, 11), (3, 3, 4))
 #: 0..12) the one on which the fewest tensors have 3 x e32 above grad_tol in the oracle's own float32 run, i.e. the batch whose whole-step
 #: gradients plain float32 resolves best (tests/test_grad_ragged.py::test_references_resolve_the_case asserts the caps).  `e0a0` and
 #: `e64a0`: among the seeds on which torch float32 also resolves every tensor of every teacher-forced STAGE to 1e-5 - on the first choice
-#: (3 and 5) one stage sum each was ill-conditioned for any float32 evaluation (same item)
+#: (3 and 5) one stage sum each was ill-conditioned for any float32 evaluation (same item).
+#: `one_obj` ... `four_obj`: reactions of 1, 2 and 4 objects.  With one object every edge is an inner edge (E == A: zero inter-object
+#: rows in every edge stage; `one_obj` is exactly one 128-row tile).  Same rule, seeds 0..9, the lowest seed among equals; `one_obj_cut`:
+#: among the seeds on which 0.3 to 0.7 of the inner edges lie inside the cutoff for the batch's and for the noised positions (1, 4, 7, 9)
 SYNTHETIC_SPECS = {s.name: s for s in (
     GradSpec("mixed", ((1, 2, 5, 17), (3, 17, 4, 9), (23, 6, 23, 33)), (0, 60, 100, 72), 196, 96, 2, 10.0, 1.5, 2, (143, 5716, 2754)),
     GradSpec("e64a64", _E64, None, 196, 96, 2, 10.0, 1.0, 1, (77, 1984, 832)),
@@ -151,6 +157,10 @@ SYNTHETIC_SPECS = {s.name: s for s in (
     GradSpec("e64a0", ((2, 1, 1), (16, 8, 10), (10, 6, 12)), None, 196, 96, 2, 10.0, 1.0, 9, (66, 1472, 640)),
     GradSpec("ones", ((1,) * 5, (1,) * 5, (1,) * 5), (0, None, None, None, None), 32, 8, 2, 10.0, 1.0, 0, (15, 30, 0)),
     GradSpec("cutoff", ((16, 1, 7), (17, 2, 31), (15, 1, 9)), None, 196, 96, 3, 5.0, 2.0, 11, (99, 4430, 1768)),
+    GradSpec("one_obj", ((8, 8, 4, 2, 2),), None, 196, 96, 2, 10.0, 1.0, 1, (24, 128, 128)),
+    GradSpec("one_obj_cut", ((23, 7, 1, 40),), None, 196, 96, 3, 5.0, 2.0, 1, (71, 2108, 2108)),
+    GradSpec("two_obj", ((9, 1, 5), (12, 30, 5)), None, 32, 8, 2, 10.0, 1.0, 0, (62, 1440, 1114)),
+    GradSpec("four_obj", ((3, 7, 2), (5, 1, 4), (6, 2, 9), (4, 8, 5)), None, 32, 32, 2, 10.0, 1.0, 3, (56, 992, 274), reflect_equiv=False),
 )}
 SYNTHETIC_CASES = list(SYNTHETIC_SPECS)
 
@@ -170,6 +180,7 @@ def oracle_grads(c, nodeframe, dtype):
     -> ({name: gradient or None}, loss, positions the dynamics was called with)."""
     import leftnet_oracle as oracle
     sd = c.state_dict(dtype)
+    node_nfs, cnf = list(getattr(c, "node_nfs", NODE_NFS)), getattr(c, "cnf", CNF)
     for k, v in sd.items():
         if v.is_floating_point() and "radial_emb" not in k:
             v.requires_grad_(True)
@@ -177,9 +188,9 @@ def oracle_grads(c, nodeframe, dtype):
 
     def dyn(xh, edge_index, t, conditions, n_frag_switch, combined_mask, edge_attr=None):
         seen.append([x[:, :3].detach().clone() for x in xh])
-        return oracle.dynamics_forward(sd, c.cfg, xh, edge_index, t, conditions, n_frag_switch, combined_mask, CNF,
+        return oracle.dynamics_forward(sd, c.cfg, xh, edge_index, t, conditions, n_frag_switch, combined_mask, cnf,
                                        nodeframe=nodeframe), None
-    dyn.pos_dim, dyn.node_nfs = 3, NODE_NFS
+    dyn.pos_dim, dyn.node_nfs = 3, node_nfs
     loss = c.loss(dyn, dtype)
     loss.backward()
     return {k: v.grad for k, v in sd.items() if v.is_floating_point() and v.requires_grad}, float(loss.detach()), seen[0]
@@ -206,8 +217,8 @@ class SyntheticGradCase:
     """A training step built from a `GradSpec` (or the name of one in SYNTHETIC_SPECS) with GradCase's interface.
     Positions N(0, 1) per atom in float64 from a seeded generator, centred per (object, reaction), times pos_scale, stored as
     float32; atom types uniform over four; the recorded draws one [n_k, 3] and one [n_k, 6] tensor per object, in the order
-    DiffusionLoss._noise asks for them.  T = 100, norm_values (1, 2, 1), scales (1, 2, 1)."""
-    T, NORM_VALUES, SCALES = 100, (1.0, 2.0, 1.0), (1.0, 2.0, 1.0)
+    DiffusionLoss._noise asks for them.  T = 100, norm_values (1, 2, 1), scales 1, 2, 1, 2, ... per object ((1, 2, 1) at three)."""
+    T, NORM_VALUES = 100, (1.0, 2.0, 1.0)
 
     def __init__(self, spec, references=True):
         spec = SYNTHETIC_SPECS[spec] if isinstance(spec, str) else spec
@@ -216,10 +227,15 @@ class SyntheticGradCase:
                         cutoff=spec.cutoff, reflect_equiv=spec.reflect_equiv)
         natm = [list(n) for n in spec.natm]
         B = self.B = len(natm[0])
-        assert len(natm) == 3 and all(len(n) == B for n in natm)
+        K = self.n_obj = len(natm)
+        assert 1 <= K <= 8 and all(len(n) == B for n in natm)
+        self.node_nfs = list(spec.node_nfs) if spec.node_nfs is not None else [9] * K
+        self.cnf = spec.condition_nf
+        self.scales = tuple((1.0, 2.0)[k % 2] for k in range(K))
+        assert len(self.node_nfs) == K
         g = torch.Generator().manual_seed(spec.seed)
         self._reps = []
-        for k in range(3):
+        for k in range(K):
             size = torch.tensor(natm[k], dtype=torch.long)
             mask = torch.repeat_interleave(torch.arange(B), size)
             n = int(size.sum())
@@ -234,11 +250,11 @@ class SyntheticGradCase:
         t_int = [d if t is None else t for t, d in zip(spec.t_int or [None] * B, t_drawn)]
         assert len(t_int) == B
         self.draws = []
-        for k in range(3):
+        for k in range(K):
             n = sum(natm[k])
-            self.draws += [torch.randn(n, 3, generator=g), torch.randn(n, 6, generator=g)]
+            self.draws += [torch.randn(n, 3, generator=g), torch.randn(n, self.node_nfs[k] - 3, generator=g)]
         self.meta = dict(name=spec.name, T=self.T, norm_values=list(self.NORM_VALUES), t_int=t_int, pos_only=False,
-                         sizes=[[natm[k][b] for k in range(3)] for b in range(B)], n_randn=len(self.draws), model_config=self.cfg)
+                         sizes=[[natm[k][b] for k in range(K)] for b in range(B)], n_randn=len(self.draws), model_config=self.cfg)
         self.seen_topology = []           # filled by _stage_checks.run: [N, E, A] of the library's topology
         if references:                    # False: the batch alone, no oracle run
             ref = _references(spec)
@@ -268,7 +284,7 @@ class SyntheticGradCase:
         return act / max(tot, 1), act, tot
 
     def state_dict(self, dtype=torch.float32):
-        return synthetic_state_dict(state_spec(self.cfg, NODE_NFS, CNF), self.cfg, seed=42, dtype=dtype)
+        return synthetic_state_dict(state_spec(self.cfg, self.node_nfs, self.cnf), self.cfg, seed=42, dtype=dtype)
 
     def reps(self, dtype, dev="cpu"):
         out = []
@@ -280,10 +296,10 @@ class SyntheticGradCase:
 
     def loss(self, dynamics, dtype, dev="cpu"):
         it = iter(self.draws)
-        dl = DiffusionLoss(dynamics, "polynomial_2", self.T, 1e-5, norm_values=self.NORM_VALUES, node_nfs=NODE_NFS, pos_only=False,
-                           scales=self.SCALES)
+        dl = DiffusionLoss(dynamics, "polynomial_2", self.T, 1e-5, norm_values=self.NORM_VALUES, node_nfs=self.node_nfs, pos_only=False,
+                           scales=self.scales)
         t_int = torch.tensor(self.meta["t_int"], dtype=dtype, device=dev).view(-1, 1)
-        nll, _ = dl.compute_loss(self.reps(dtype, dev), torch.zeros(self.B, 1, dtype=dtype, device=dev), training=True, t_int=t_int,
+        nll, _ = dl.compute_loss(self.reps(dtype, dev), torch.zeros(self.B, max(self.cnf, 1), dtype=dtype, device=dev), training=True, t_int=t_int,
                                  draw=lambda shape: next(it).to(device=dev, dtype=dtype))
         return nll.mean(0)
 

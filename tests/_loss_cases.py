@@ -23,12 +23,28 @@ LAYOUTS = {
     "empty_group": ([[2, 0], [2, 3], [1, 2]], [9, 9, 9]),             # object 0 is empty in sample 1; object 2 has one atom in sample 0
     "widest": ([[3, 65], [2, 1], [64, 5]], [WIDEST_NF] * 3),          # 64 atoms: every lane once; 65: one lane twice
 }
+#: reactions of 1, 2, 4 and 8 objects instead of three (the library takes 1 to 8): the kernels' object loop, the per-object pointer
+#: tables and the (sample, object) group table at every count.  Kept apart from LAYOUTS: their fixed masks differ (`fixed_masks`).  The loss
+#: entries need a class column (node_nf >= 5), so the narrowest object of `four_objects` has 5 where the wrapper alone would take 4.
+OBJECT_LAYOUTS = {
+    "one_object": ([[8, 1, 17, 5]], [9]),
+    "two_objects": ([[9, 0, 5], [12, 7, 5]], [7, 12]),                # object 0 is empty in sample 1
+    "four_objects": ([[2, 3, 6], [1, 4, 3], [3, 0, 5], [2, 2, 7]], [5, WIDEST_NF, 9, 6]),
+    "eight_objects": ([[k + 1, 8 - k] for k in range(8)], [9] * 8),   # groups of 1 to 8 atoms
+}
+#: layout -> (condition_nf, model_config overrides) of the module whose oard_config the kernel tests pass; default (1, {}).
+#: four_objects: embedding 10 + t + 5 conditions fill all 16 columns of in_hidden_channels = 16
+OBJECT_MODEL = {"two_objects": (0, {}), "four_objects": (5, {"in_hidden_channels": 16})}
 #: every layout sees t = 0 (at least twice in one batch), 1, a middle step and T; ragged[0] puts t = 0 on the 70 / 130-atom sample
 T_INTS = {
     "ragged": [[0, 500, 0, 1000, 0], [1, 0, 500, 0, 1000]],
     "mixed_nf": [[0, 500, 0, 1000, 0], [1, 0, 500, 0, 1000]],
     "empty_group": [[0, 0], [1, 1000], [500, 0]],
     "widest": [[0, 0], [1, 1000], [0, 500]],
+    "one_object": [[0, 500, 0, 1000], [1, 0, 500, 0]],
+    "two_objects": [[0, 0, 500], [1, 1000, 0]],
+    "four_objects": [[0, 0, 500], [1, 1000, 0]],
+    "eight_objects": [[0, 0], [1, 1000], [500, 0]],
 }
 #: the one trainer-level case off the fixtures (test_trainer_fused.py): the network runs, so three objects of node_nf = 9
 TRAINER = "trainer_ragged"
@@ -39,14 +55,33 @@ BIASES = ((0.0, 0.0, 0.0), (0.0, 0.5, 0.0))
 FIXED = {0: [], 0b010: [1], 0b101: [0, 2]}      # fixed_mask -> fixed_idx
 #: seeds of the inputs, chosen so that test_inputs_keep_clear_of_the_float32_discontinuities holds for every case (a draw within
 #: ~2e-4 of zero on the charge column of a t = 0 atom would not)
-SEEDS = {"ragged": 101, "mixed_nf": 102, "empty_group": 103, "widest": 104, TRAINER: 105}
+SEEDS = {"ragged": 101, "mixed_nf": 102, "empty_group": 103, "widest": 104, TRAINER: 105,
+         "one_object": 106, "two_objects": 107, "four_objects": 108, "eight_objects": 109}
+
+
+def scales(K):
+    """1, 2, 1, 2, ... per object: SCALES at three."""
+    return tuple((1.0, 2.0)[k % 2] for k in range(K))
+
+
+def fixed_idx(fixed_mask):
+    return [k for k in range(8) if (fixed_mask >> k) & 1]
+
+
+def fixed_masks(layout):
+    """LAYOUTS: FIXED's three.  OBJECT_LAYOUTS: nothing fixed, one object (the second, or the only one), every even and every odd one."""
+    if layout not in OBJECT_LAYOUTS:
+        return list(FIXED)
+    K = len(OBJECT_LAYOUTS[layout][0])
+    every = (1 << K) - 1
+    return list(dict.fromkeys([0, 1 << min(1, K - 1), 0x55 & every, 0xAA & every]))
 
 
 def cases(layout):
     """Every (t_int, precision, norm_biases, pos_only, fixed_mask) of a layout."""
     if layout == TRAINER:
         return [TRAINER_CASE]
-    return list(itertools.product(T_INTS[layout], PRECISIONS, BIASES, (0, 1), FIXED))
+    return list(itertools.product(T_INTS[layout], PRECISIONS, BIASES, (0, 1), fixed_masks(layout)))
 
 
 def tag(case):
@@ -59,7 +94,7 @@ class Batch:
     kernels take the draws as an argument; the clamp keeps every cdf difference of a live t = 0 term above ~5e-3 at sigma_0 = 0.22)."""
 
     def __init__(self, layout):
-        frags, self.node_nfs = TRAINER_LAYOUT if layout == TRAINER else LAYOUTS[layout]
+        frags, self.node_nfs = TRAINER_LAYOUT if layout == TRAINER else (LAYOUTS.get(layout) or OBJECT_LAYOUTS[layout])
         self.layout = layout
         g = torch.Generator().manual_seed(SEEDS[layout])
         self.sizes = [torch.tensor(f) for f in frags]
@@ -141,7 +176,7 @@ def loss_object(batch, case, net, cls=None):
     t_int, precision, biases, pos_only, fixed_mask = case
     cls = cls or (WideLoss if max(batch.node_nfs) > 9 else DiffusionLoss)
     return cls(Stub(batch.node_nfs, net), "polynomial_2", T, precision, norm_values=NORM_VALUES, norm_biases=biases,
-               pos_only=bool(pos_only), fixed_idx=FIXED[fixed_mask], scales=SCALES)
+               pos_only=bool(pos_only), fixed_idx=fixed_idx(fixed_mask), scales=scales(batch.K))
 
 
 def reference(batch, case, dtype, b_total=None, cls=None):
@@ -162,9 +197,9 @@ def reference(batch, case, dtype, b_total=None, cls=None):
     dnet = [x.grad * (B / b_total) for x in net]
     err_t = [e.detach() for e in lt["error_t"]]
     width = [POS if dl.pos_only else POS + nf for nf in batch.node_nfs]
-    err_n = [err_t[k] / (width[k] * reps[k]["size"]) * SCALES[k] for k in range(K)]
+    err_n = [err_t[k] / (width[k] * reps[k]["size"]) * dl.scales[k] for k in range(K)]
     for k in range(K):                                     # the rows ARE what compute_loss logs
-        assert abs(float(err_n[k].mean() / (SCALES[k] + 1e-4)) - info[f"error_t_{k}"]) <= 1e-6 * abs(info[f"error_t_{k}"]) + 1e-30
+        assert abs(float(err_n[k].mean() / (dl.scales[k] + 1e-4)) - info[f"error_t_{k}"]) <= 1e-6 * abs(info[f"error_t_{k}"]) + 1e-30
         assert abs(float(err_t[k].mean()) - info[f"unorm_error_t_{k}"]) <= 1e-6 * abs(info[f"unorm_error_t_{k}"]) + 1e-30
     return {"z": z, "eps": eps, "dnet": dnet, "nll": nll.detach(), "terms": torch.stack(err_n + err_t)}
 

@@ -41,8 +41,10 @@ def run(name, log=print, clobber=False):
     c = GradCase(name) if isinstance(name, str) else name
     name = c.name
     dev = torch.device("cuda:0")
-    dyn = EGNNDynamics(model_config=dict(c.cfg), fragment_names=["R", "TS", "P"], node_nfs=NODE_NFS, edge_nf=0,
-                       condition_nf=CNF, device=dev)
+    node_nfs, cnf = list(getattr(c, "node_nfs", NODE_NFS)), getattr(c, "cnf", CNF)     # a synthetic case may have 1 to 8 objects
+    n_obj = len(node_nfs)
+    dyn = EGNNDynamics(model_config=dict(c.cfg), fragment_names=["R", "TS", "P"] if n_obj == 3 else [f"o{k}" for k in range(n_obj)],
+                       node_nfs=node_nfs, edge_nf=0, condition_nf=cnf, device=dev)
     dyn.load_state_dict(c.state_dict(), strict=True)
     keep = {}
     orig = training.DynamicsFunction.forward
@@ -69,7 +71,7 @@ def run(name, log=print, clobber=False):
     P64 = {k: v.double() for k, v in P.items()}
     log(f"{name}: N {N} E {E} A {A} loss {float(loss.detach()):.8f} ref64 {c.f64_loss:.8f}")
     geo = tape.get(_capi.TAPE_GEO)[:A]
-    gargs = (topo.inner_src, topo.inner_tgt, topo.node_sample, topo.node_group, topo.B, topo.B * 3)
+    gargs = (topo.inner_src, topo.inner_tgt, topo.node_sample, topo.node_group, topo.B, topo.B * n_obj)
     rbf_t, pp0_t, x1_t = tape.get(_capi.TAPE_RBF)[:A, :R], tape.get(_capi.TAPE_PP0)[:, 0], tape.get(_capi.TAPE_X1)
     g = refs.Geometry(*gargs, geo, rbf_t, pp0_t, x1_t)
     g64 = refs.Geometry(*gargs, geo.double(), rbf_t.double(), pp0_t.double(), x1_t.double())
@@ -309,7 +311,7 @@ def run(name, log=print, clobber=False):
         gate(f"bwd layer {l} node pre", ["ds_in"] + [short(n_) for n_ in pn], [unpad(ds_o)] + [cut(n_, gt[n_]) for n_ in pn],
              [g32[0]] + [cut(n_, t_) for n_, t_ in zip(pn, g32[1:])], [g64_[0]] + [cut(n_, t_) for n_, t_ in zip(pn, g64_[1:])])
     # ---- tail (output block + velocity / CoM + decoders) and init head + encoders ----------------------------------------
-    n_obj, emb = len(NODE_NFS), dyn.embed_dim
+    emb = dyn.embed_dim
     dec = [dyn._module_prefix("decoders", k) for k in range(n_obj)]
     enc = [dyn._module_prefix("encoders", k) for k in range(n_obj)]
     tn = [n_ for n_ in P if n_.startswith(("model.out_pos.", "model.embedding_out.", *dec))]

@@ -18,7 +18,7 @@ T = lc.T
 POS = lc.POS
 NORM_VALUES = (2.0, 4.0, 10.0)        # norm_values[0] != 1: delta_log_px = -(N - 1) 3 log 2
 SCALES = lc.SCALES
-LAYOUTS = lc.LAYOUTS
+LAYOUTS, OBJECT_LAYOUTS, OBJECT_MODEL = lc.LAYOUTS, lc.OBJECT_LAYOUTS, lc.OBJECT_MODEL
 PRECISIONS, BIASES, FIXED = lc.PRECISIONS, lc.BIASES, lc.FIXED
 #: evaluation draws t_int in [1, T]: every layout sees 1, a middle step and T
 T_INTS = {
@@ -26,13 +26,18 @@ T_INTS = {
     "mixed_nf": [[1, 500, 1000, 1, 500], [1000, 1, 500, 1000, 1]],
     "empty_group": [[1, 1000], [500, 1]],
     "widest": [[1000, 500], [1, 1000]],
+    "one_object": [[1, 500, 1000, 1], [1000, 1, 500, 1000]],
+    "two_objects": [[1, 500, 1000], [1000, 1, 500]],
+    "four_objects": [[1, 500, 1000], [1000, 1, 500]],
+    "eight_objects": [[1, 1000], [500, 1]],
 }
 TRAINER = lc.TRAINER
 TRAINER_CASE = ([1, 500, 1000], 0.05, (0.0, 0.5, 0.0), 0, 0b010)
 #: seeds of the second noise block (z_0) and the second network output, chosen so that
 #: test_vlb_cases_cpu.test_inputs_keep_clear_of_the_float32_discontinuities holds for EVERY case - in evaluation every atom of every
 #: sample has the t = 0 terms, so a draw within ~3e-4 of zero on any charge column would not
-SEEDS0 = {"ragged": 201, "mixed_nf": 202, "empty_group": 203, "widest": 204, TRAINER: 205}
+SEEDS0 = {"ragged": 201, "mixed_nf": 202, "empty_group": 203, "widest": 204, TRAINER: 205,
+          "one_object": 206, "two_objects": 207, "four_objects": 208, "eight_objects": 209}
 TERM_KEYS = ("error_t", "loss_0_x", "loss_0_cat", "loss_0_charge")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -41,7 +46,7 @@ def cases(layout):
     """Every (t_int, precision, norm_biases, pos_only, fixed_mask) of a layout."""
     if layout == TRAINER:
         return [TRAINER_CASE]
-    return list(itertools.product(T_INTS[layout], PRECISIONS, BIASES, (0, 1), FIXED))
+    return list(itertools.product(T_INTS[layout], PRECISIONS, BIASES, (0, 1), lc.fixed_masks(layout)))
 
 
 tag = lc.tag
@@ -113,7 +118,7 @@ def loss_object(batch, case, dtype):
     cls = _capturing(lc.WideLoss if max(batch.node_nfs) > 9 else DiffusionLoss)
     stub = TwoCallStub(batch.node_nfs, [x.to(dtype) for x in batch.net], [x.to(dtype) for x in batch.net0])
     return cls(stub, "polynomial_2", T, precision, norm_values=NORM_VALUES, norm_biases=biases, pos_only=bool(pos_only),
-               fixed_idx=FIXED[fixed_mask], scales=SCALES)
+               fixed_idx=lc.fixed_idx(fixed_mask), scales=lc.scales(batch.K))
 
 
 def vlb_table(dl, reps, cond, t_int, draw, floor_sizes=False):

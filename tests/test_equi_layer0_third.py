@@ -93,7 +93,8 @@ def test_ragged_production_dims_off_equals_on(sizes, pos_scale, num_layers):
 
 
 @pytest.mark.parametrize("shapes", ["throughput", "auto"])
-@pytest.mark.parametrize("name", ["g2_prod_b2_n23", "g3p_prod_cutoff", "g10p_noreflect_prod", "g10_noreflect_h32", "g6_h32_r32"])
+@pytest.mark.parametrize("name", ["g2_prod_b2_n23", "g3p_prod_cutoff", "g10p_noreflect_prod", "g10_noreflect_h32", "g6_h32_r32",
+                                  "g13_one_object", "g13_eight_objects"])
 def test_golden_cases_off_equals_on(name, shapes):
     """The committed fixtures, among them reflect_equiv = False (the XC instantiation of the node kernel) at both widths - under the
     throughput shapes, which take the shortcut, and under the library's default launch heuristics, which send these small cases to the

@@ -45,7 +45,8 @@ def _flat(out):
     return torch.cat([o.double().reshape(-1).cpu() for o in out])
 
 
-@pytest.mark.parametrize("name,l0", [("g3_cutoff_ragged", 1), ("g2_prod_b2_n23", 1), ("g2_prod_b2_n23", 0)])
+@pytest.mark.parametrize("name,l0", [("g3_cutoff_ragged", 1), ("g2_prod_b2_n23", 1), ("g2_prod_b2_n23", 0),
+                                     ("g13_one_object", 1), ("g13_eight_objects", 1)])
 def test_golden_cases_on_and_off(name, l0):
     """H = 32 / R = 8 (no 4-row tiles, ragged active list) and the production widths (H = 196: the 13th tile of every third has 4 real
     rows) with layer 0's skipped third on and off."""

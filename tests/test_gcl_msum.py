@@ -98,9 +98,9 @@ def _gate(out, cfg, sd, batch):
 RAGGED = [[1, 3, 23], [2, 17, 23], [5, 4, 23]]
 
 
-@pytest.mark.parametrize("name", ["g6_h32_r32", "g10_noreflect_h32", "g2_prod_b2_n23"])
+@pytest.mark.parametrize("name", ["g6_h32_r32", "g10_noreflect_h32", "g2_prod_b2_n23", "g13_one_object", "g13_eight_objects"])
 def test_golden_cases_on_and_off_pass_the_gate(name):
-    """The committed fixtures (H = 32 twice, 196 x 96 once), throughput shapes pinned, option off and on: both inside the fixture's gate
+    """The committed fixtures (H = 32 twice, 196 x 96 once; one object: no inter-object column at all, CX = 0; eight objects), throughput shapes pinned, option off and on: both inside the fixture's gate
     against the float64 reference; the difference between the two forms is printed (profiles/gcl_msum.txt)."""
     dev = torch.device("cuda:0")
     c = Case(name)

@@ -19,7 +19,7 @@ GENERAL_CASES = ["g11_edge_cutoff_h32", "g11p_edge_cutoff_prod", "g11_random_sub
 def _dyn(c, dev, path="auto"):
     from oareactdiff_amd.dynamics import EGNNDynamics
     d = EGNNDynamics(model_config=dict(c.cfg), fragment_names=[f"o{k}" for k in range(c.n_obj)], node_nfs=c.node_nfs, edge_nf=0,
-                     condition_nf=c.cnf, device=dev)
+                     condition_nf=c.cnf, condition_time=c.condition_time, device=dev)
     d.load_state_dict(c.state_dict(), strict=True)
     d.edge_list_path = path
     return d

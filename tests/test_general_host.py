@@ -30,7 +30,7 @@ def harness(tmp_path_factory):
 def run_host(harness, c: Case, edge_index=None):
     from oareactdiff_amd.dynamics import EGNNDynamics
     dyn = EGNNDynamics(model_config=dict(c.cfg), fragment_names=[f"o{k}" for k in range(c.n_obj)], node_nfs=c.node_nfs, edge_nf=0,
-                       condition_nf=c.cnf, device=torch.device("cpu"))
+                       condition_nf=c.cnf, condition_time=c.condition_time, device=torch.device("cpu"))
     dyn.load_state_dict(c.state_dict(), strict=True)
     cfg = dyn._config()
     tensors = [t.detach().float().contiguous() if t is not None else None for t in dyn._ordered_tensors()]

@@ -15,7 +15,7 @@ TOL = 1e-5
 def _dyn(c, dev):
     from oareactdiff_amd.dynamics import EGNNDynamics
     d = EGNNDynamics(model_config=dict(c.cfg), fragment_names=[f"o{k}" for k in range(c.n_obj)],
-                     node_nfs=c.node_nfs, edge_nf=0, condition_nf=c.cnf, device=dev)
+                     node_nfs=c.node_nfs, edge_nf=0, condition_nf=c.cnf, condition_time=c.condition_time, device=dev)
     d.load_state_dict(c.state_dict(), strict=True)
     return d
 
@@ -48,7 +48,8 @@ def test_forward_matches_reference_f64(name, shapes):
           f"h {rel(h, h32):.2e} | ref32-vs-ref64 vel {rel(v32, rv):.2e} h {rel(h32, rh):.2e}")
 
 
-@pytest.mark.parametrize("name", ["g1_wrapper_small", "g2s_prod_b1_n5", "g3_cutoff_ragged", "g3p_prod_cutoff"])
+@pytest.mark.parametrize("name", ["g1_wrapper_small", "g2s_prod_b1_n5", "g3_cutoff_ragged", "g3p_prod_cutoff",
+                                  "g13_one_object", "g13_two_objects_nocond", "g13_four_objects_wide", "g13_eight_objects", "g13_no_time"])
 def test_stages_match_oracle(name):
     """Intermediate tensors (taps) against the float64 oracle evaluated on the same inputs."""
     from oareactdiff_amd import _capi
@@ -58,7 +59,7 @@ def test_stages_match_oracle(name):
     st = {}
     oracle.dynamics_forward(c.state_dict(torch.float64), c.cfg, [x.double() for x in c.xh], c.edge_index,
                             c.t.double(), c.conditions.double(), c.n_frag_switch, c.combined_mask, c.cnf,
-                            nodeframe="exact", stages=st)
+                            condition_time=c.condition_time, nodeframe="exact", stages=st)
     H, nl = c.cfg["hidden_channels"], c.cfg["num_layers"]
     L = _capi.lib()
     try:

@@ -2,7 +2,8 @@
 formulas of include/oard.h restated here in float64 plain torch.  The network never runs: the narrowest built width pair, one layer.
 
 Layouts: different atom counts per object, an empty (sample, object) group with node_nfs 4 / 5 / 6, groups of 1024 / 1 / 129 atoms, and
-B = 64 x 3 x 23 split into 1, 2, 3 and 4 sub-batches (one launch per sub-batch, one wavefront per group).
+B = 64 x 3 x 23 split into 1, 2, 3 and 4 sub-batches (one launch per sub-batch, one wavefront per group); and 1, 2, 4 and 8 objects per
+reaction instead of three, where `fixed_mask` (one bit per object) runs over no bit, every single bit, all bits and, at eight, 0b10101010.
 
 Gate of every output tensor (the rule of tests/test_sampler_step.py): err(x) = max|x - ref64| / max|ref64|; the same formulas in torch
 float32 on the CPU give e32; required is err(kernel) <= max(4 e32, 2^-21).
@@ -30,6 +31,10 @@ LAYOUTS = {
     "wrapper": ([[2, 0], [2, 3], [1, 2]], [4, 5, 6], 3),              # object 0 is empty in sample 1
     "groups_1024_1_129": ([[1024], [1], [129]], [9, 9, 9], 1),        # the largest group, one atom, two passes of the 64 lanes + 1
     "b64": ([[23] * 64] * 3, [9, 9, 9], 1),
+    "one_object": ([[8, 1, 17, 5]], [9], 1),
+    "two_objects": ([[9, 0, 5], [12, 7, 5]], [7, 12], 0),             # object 0 is empty in sample 1; no conditions
+    "four_objects": ([[2, 3, 6], [1, 4, 3], [3, 0, 5], [2, 2, 7]], [4, 19, 9, 6], 5, dict(NARROW, in_hidden_channels=16)),
+    "eight_objects": ([[k + 1, 8 - k] for k in range(8)], [9] * 8, 1),                              # groups of 1 to 8 atoms
 }
 FLOOR = 2.0 ** -21
 COM = 2.0 ** -23
@@ -37,6 +42,14 @@ POS = 3
 GUARD = 3                       # NaN rows behind every output tensor
 MASKS = (0, 0b101, 0b010, 0b111)
 OPERANDS = ("z", "eh", "xfix", "nk", "ns", "nj")
+
+
+def object_masks(n_obj):
+    """No bit, every single bit, all bits; at eight objects also every other bit."""
+    masks = [0] + [1 << k for k in range(n_obj)] + [(1 << n_obj) - 1]
+    if n_obj == 8:
+        masks.append(0b10101010)
+    return tuple(dict.fromkeys(masks))
 
 
 def coefficient_rows():
@@ -57,15 +70,17 @@ class Rig:
 
     def __init__(self, layout, dev):
         from oareactdiff_amd import EGNNDynamics
-        frags, self.node_nfs, cnf = LAYOUTS[layout]
+        frags, self.node_nfs, cnf = LAYOUTS[layout][:3]
+        model_config = LAYOUTS[layout][3] if len(LAYOUTS[layout]) > 3 else NARROW
         self.dev = dev
         frag = [torch.tensor(f) for f in frags]
         self.masks = [get_mask_for_frag(f) for f in frag]
         cm = torch.cat(self.masks)
         self.n_groups = len(frags[0])
         self.n_obj = len(self.node_nfs)
-        self.dyn = EGNNDynamics(model_config=dict(NARROW), fragment_names=["R", "TS", "P"], node_nfs=self.node_nfs, edge_nf=0,
-                                condition_nf=cnf, device=dev)
+        self.dyn = EGNNDynamics(model_config=dict(model_config),
+                                fragment_names=["R", "TS", "P"] if self.n_obj == 3 else [f"o{k}" for k in range(self.n_obj)],
+                                node_nfs=self.node_nfs, edge_nf=0, condition_nf=cnf, device=dev)
         keys = (get_edges_index(cm, remove_self_edge=True).to(dev), get_n_frag_switch(frag).to(dev), cm.to(dev))
         with torch.cuda.device(dev):
             self.stream = torch.cuda.current_stream(dev).cuda_stream
@@ -170,7 +185,7 @@ def check_com(got, masks, n_groups, fixed_mask, jump, where):
     return worst
 
 
-def sweep(rig, title, offsets=(0.0, 60.0), coef_names=("first", "middle"), entries=("raw", "dev")):
+def sweep(rig, title, offsets=(0.0, 60.0), coef_names=("first", "middle"), entries=("raw", "dev"), masks=MASKS):
     """fixed_mask x jump x zero_feature_noise x h0 given / None x coefficient rows x input sets.  Returns the raw entry's outputs."""
     kept, worst_err, worst_ratio, worst_com = [], 0.0, 0.0, {}
     ng = rig.n_groups
@@ -178,10 +193,10 @@ def sweep(rig, title, offsets=(0.0, 60.0), coef_names=("first", "middle"), entri
     for offset in offsets:
         cpu, ops = rig.inputs(17 + int(offset), offset)
         before = {k: [t.clone() for t in v] for k, v in ops.items()}
-        for cname, fixed_mask, jump, zero_h, use_h0 in itertools.product(coef_names, MASKS, (0, 1), (0, 1), (False, True)):
+        for cname, fixed_mask, jump, zero_h, use_h0 in itertools.product(coef_names, masks, (0, 1), (0, 1), (False, True)):
             coef = list(rows[cname])
             coef[5] = float(jump)
-            where = f"{title} offset {offset} coefficients {cname} fixed {fixed_mask:03b} jump {jump} zero_feature_noise {zero_h} h0 {use_h0}"
+            where = f"{title} offset {offset} coefficients {cname} fixed {fixed_mask:0{rig.n_obj}b} jump {jump} zero_feature_noise {zero_h} h0 {use_h0}"
             rc, got = rig.launch(ops, fixed_mask, coef, zero_h, use_h0, "raw")
             assert rc == _capi.OARD_OK, where
             kept.append(got)
@@ -217,6 +232,20 @@ def sweep(rig, title, offsets=(0.0, 60.0), coef_names=("first", "middle"), entri
 @pytest.mark.parametrize("layout", ["ragged", "wrapper", "groups_1024_1_129"])
 def test_fused_step_matches_its_float64_formula(layout):
     sweep(Rig(layout, torch.device("cuda:0")), layout)
+
+
+@pytest.mark.parametrize("layout", ["one_object", "two_objects", "four_objects", "eight_objects"])
+def test_fused_step_with_other_object_counts(layout):
+    rig = Rig(layout, torch.device("cuda:0"))
+    masks = object_masks(rig.n_obj)
+    assert len(masks) == {1: 2, 2: 4, 4: 6, 8: 11}[rig.n_obj]
+    sweep(rig, layout, masks=masks)
+    # a bit beyond the objects is refused, at every object count (at eight there is no such bit in the 8-bit mask: bit 8)
+    _, ops = rig.inputs(3, 0.0)
+    scratch = [torch.zeros_like(x) for x in ops["z"]]
+    row = coefficient_rows()["middle"]
+    for entry in ("raw", "dev"):
+        assert rig.launch(ops, 1 << rig.n_obj, row, 0, False, entry, out=scratch)[0] == _capi.OARD_EINVAL
 
 
 def test_sub_batches_give_identical_bits():
@@ -273,3 +302,8 @@ def test_bad_arguments_are_refused():
 #   wrapper             2.77e-06   2.29   1.77e-08 / 1.81e-08
 #   groups_1024_1_129   1.93e-06   1.74   4.57e-09 / 6.12e-09
 #   b64 (any parts)     2.00e-06   1.54   1.47e-08 / 1.18e-08
+# and over object_masks(n_obj) in place of the four masks:
+#   one_object          2.04e-06   1.36   1.04e-08 / 1.86e-08
+#   two_objects         2.99e-06   1.14   2.28e-08 / 2.21e-08
+#   four_objects        5.61e-06   2.16   2.78e-08 / 2.45e-08
+#   eight_objects       3.49e-06   2.08   2.65e-08 / 2.53e-08

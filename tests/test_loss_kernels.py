@@ -36,7 +36,7 @@ PAD, COL0 = 3, 2                      # `terms` has B_total = B + PAD columns, t
 
 
 # ---- CPU-only checks of the inputs and of the restated reference --------------------------------------------------------------------
-@pytest.mark.parametrize("layout", list(lc.LAYOUTS) + [lc.TRAINER])
+@pytest.mark.parametrize("layout", list(lc.LAYOUTS) + [lc.TRAINER] + list(lc.OBJECT_LAYOUTS))
 def test_inputs_keep_clear_of_the_float32_discontinuities(layout):
     """In the float64 reference, for every atom of a t = 0 sample of every case: the charge estimate that `.long()` truncates lies at
     least 2^-20 |value| from every non-zero integer (truncation is continuous at 0), and every cdf difference under a log is above
@@ -87,8 +87,9 @@ class Rig:
         self.capi, self.L = _capi, _capi.lib()
         self.batch = b = lc.Batch(layout)
         self.dev = dev
-        self.dyn = EGNNDynamics(model_config=dict(NARROW), fragment_names=["R", "TS", "P"], node_nfs=b.node_nfs, edge_nf=0, condition_nf=1,
-                                device=dev)
+        cnf, over = lc.OBJECT_MODEL.get(layout, (1, {}))
+        self.dyn = EGNNDynamics(model_config=dict(NARROW, **over), fragment_names=["R", "TS", "P"] if b.K == 3 else [f"o{k}" for k in range(b.K)],
+                                node_nfs=b.node_nfs, edge_nf=0, condition_nf=cnf, device=dev)
         self.cfg = self.dyn._config()
         with torch.cuda.device(dev):
             self.stream = torch.cuda.current_stream(dev).cuda_stream
@@ -147,7 +148,7 @@ class Rig:
         nll = torch.full((b.B,), float("nan"), device=self.dev)
         terms = torch.full((2 * b.K, b.B + PAD), float("nan"), device=self.dev)
         dnet = self.nan_like()
-        sc = (C.c_float * b.K)(*lc.SCALES[:b.K])
+        sc = (C.c_float * b.K)(*lc.scales(b.K))
         with torch.cuda.device(self.dev):
             rc = self.L.oard_loss_terms(C.byref(cfg or self.cfg), topo or self.topo.handle, self.arr(eps) if have_eps else None, self.arr(net),
                                         self.arr(z), self.arr(self.one_hot), self.arr(self.charge), t.data_ptr(),
@@ -258,7 +259,7 @@ def test_widest_node_nf_is_the_widest_supported():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("layout", list(lc.LAYOUTS))
+@pytest.mark.parametrize("layout", list(lc.LAYOUTS) + list(lc.OBJECT_LAYOUTS))
 def test_prepare_matches_float64(layout):
     rig, worst = _rig(layout), Worst()
     for case in lc.cases(layout):
@@ -271,7 +272,7 @@ def test_prepare_matches_float64(layout):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("layout", list(lc.LAYOUTS))
+@pytest.mark.parametrize("layout", list(lc.LAYOUTS) + list(lc.OBJECT_LAYOUTS))
 def test_terms_match_float64(layout):
     """The kernel is fed the float32 roundings of the reference's z, eps and net."""
     rig, worst = _rig(layout), Worst()
@@ -288,7 +289,7 @@ def test_terms_match_float64(layout):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("layout", list(lc.LAYOUTS))
+@pytest.mark.parametrize("layout", list(lc.LAYOUTS) + list(lc.OBJECT_LAYOUTS))
 def test_prepare_then_terms_chain(layout):
     """The kernel's own z and eps into oard_loss_terms: the same gates."""
     rig, worst = _rig(layout), Worst()
@@ -352,5 +353,9 @@ def test_inputs_are_not_mutated_and_bad_arguments_are_refused():
 # mixed_nf        9.15e-08 (7.93e-08) 0.19    4.93e-08 (4.93e-08) 0.10   2.72e-07 (8.69e-08) 0.57   6.17e-08 (3.78e-08) 0.13   8.74e-08 (5.05e-08) 0.18
 # empty_group     9.44e-08 (9.44e-08) 0.20    4.48e-08 (4.48e-08) 0.09   2.30e-07 (5.37e-08) 0.48   1.12e-07 (1.12e-07) 0.23   1.38e-07 (1.38e-07) 0.25
 # widest          9.35e-08 (9.35e-08) 0.20    5.13e-08 (5.13e-08) 0.11   2.12e-07 (2.12e-07) 0.34   4.27e-08 (3.50e-08) 0.09   1.11e-07 (6.13e-08) 0.23
+# one_object      1.10e-07 (7.46e-08) 0.23    3.66e-08 (3.66e-08) 0.08   2.27e-07 (3.01e-07) 0.41   8.71e-08 (5.22e-08) 0.18   3.77e-08 (3.87e-08) 0.08
+# two_objects     7.21e-08 (8.92e-08) 0.15    7.24e-08 (6.35e-08) 0.15   2.71e-07 (5.95e-08) 0.57   8.48e-08 (8.48e-08) 0.18   9.39e-08 (9.39e-08) 0.20
+# four_objects    1.01e-07 (8.42e-08) 0.21    4.32e-08 (4.32e-08) 0.09   2.73e-07 (9.34e-08) 0.57   7.86e-08 (7.86e-08) 0.16   8.53e-08 (8.53e-08) 0.18
+# eight_objects   1.14e-07 (8.72e-08) 0.24    4.09e-08 (4.09e-08) 0.09   2.48e-07 (5.61e-08) 0.52   1.17e-07 (9.80e-08) 0.25   1.20e-07 (5.10e-08) 0.25
 # The chained run (the kernel's own z and eps) gives the same nll and dnet figures; its terms: ragged 7.79e-08 (3.29e-08) 0.16.
 # All of it - the four layouts, 240 cases, three tests - takes 1.5 s of test time.

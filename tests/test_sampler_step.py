@@ -1,7 +1,8 @@
 """The element-wise sampler kernel (k_sampler_step behind oard_sampler_step / oard_sampler_step_dev) and oard_nan_replace, every mode
 against the formulas of include/oard.h restated here in float64 plain torch - on layouts the golden fixtures do not have: different
 atom counts per object, an empty (sample, object) group, 1-atom / 129-atom / 1024-atom groups, and a B = 64 batch split into 1, 2, 3
-and 4 sub-batches (the step launches once per sub-batch).
+and 4 sub-batches (the step launches once per sub-batch); and with 1, 2, 4 and 8 objects per reaction instead of three (the object
+loop, the per-object pointer tables and the group table `n_groups = B x n_obj` at every count the library takes).
 
 The gate of every output tensor: err(x) = max|x - ref64| / max|ref64|; the same formulas in torch float32 on the CPU give e32;
 required is err(kernel) <= max(4 e32, 2^-21) - the factor covers the different summation order of the group means (the kernel sums a
@@ -21,12 +22,17 @@ pytestmark = pytest.mark.gpu
 
 # the network is never run here: the narrowest built width pair, one layer
 NARROW = dict(pos_require_grad=False, cutoff=5.0, num_layers=1, hidden_channels=32, num_radial=8, in_hidden_channels=8)
-#           atoms per sample of R, TS, P                                        node_nfs   condition_nf
+WIDE = dict(NARROW, in_hidden_channels=16)           # embedding 10 + t + 5 conditions: all 16 columns of h_in in use
+#           atoms per sample of each object (R, TS, P)                          node_nfs   condition_nf  [model_config]
 LAYOUTS = {
     "ragged": ([[7, 23, 12, 1, 16], [9, 20, 5, 3, 16], [4, 23, 12, 2, 30]], [9, 9, 9], 1),
     "wrapper": ([[2, 0], [2, 3], [1, 2]], [4, 5, 6], 3),              # golden g1_wrapper_small: object 0 is empty in sample 1
     "groups_1024_1_129": ([[1024], [1], [129]], [9, 9, 9], 1),        # OARD_MAX_GROUP, one atom, one more than a 128-thread block
     "b64": ([[23] * 64] * 3, [9, 9, 9], 1),                           # the benchmark's batch: 4 sub-batches by default
+    "one_object": ([[8, 1, 17, 5]], [9], 1),                          # every edge is an inner edge
+    "two_objects": ([[9, 0, 5], [12, 7, 5]], [7, 12], 0),             # object 0 is empty in sample 1; no conditions
+    "four_objects": ([[2, 3, 6], [1, 4, 3], [3, 0, 5], [2, 2, 7]], [4, 19, 9, 6], 5, WIDE),       # feature widths 1 and 16 side by side
+    "eight_objects": ([[k + 1, 8 - k] for k in range(8)], [9] * 8, 1),                              # groups of 1 to 8 atoms
 }
 MODES = {0: "ancestral step", 1: "final x|z0", 2: "initial noise", 3: "q(z_s|x)", 4: "forward jump"}
 FLOOR = 2.0 ** -21
@@ -45,14 +51,16 @@ class Rig:
 
     def __init__(self, layout, dev):
         from oareactdiff_amd import DiffusionSampler, EGNNDynamics
-        frags, self.node_nfs, cnf = LAYOUTS[layout]
+        frags, self.node_nfs, cnf = LAYOUTS[layout][:3]
+        model_config = LAYOUTS[layout][3] if len(LAYOUTS[layout]) > 3 else NARROW
+        n_obj = len(frags)
         self.dev = dev
         frag = [torch.tensor(f) for f in frags]
         self.masks = [get_mask_for_frag(f) for f in frag]
         cm = torch.cat(self.masks)
         self.n_groups = len(frags[0])
-        self.dyn = EGNNDynamics(model_config=dict(NARROW), fragment_names=["R", "TS", "P"], node_nfs=self.node_nfs, edge_nf=0,
-                                condition_nf=cnf, device=dev)
+        self.dyn = EGNNDynamics(model_config=dict(model_config), fragment_names=["R", "TS", "P"] if n_obj == 3 else [f"o{k}" for k in range(n_obj)],
+                                node_nfs=self.node_nfs, edge_nf=0, condition_nf=cnf, device=dev)
         self.smp = {z: DiffusionSampler(self.dyn, "polynomial_2", 1000, 1e-5, pos_only=bool(z)) for z in (0, 1)}
         self.keys = (get_edges_index(cm, remove_self_edge=True).to(dev), get_n_frag_switch(frag).to(dev), cm.to(dev))
         with torch.cuda.device(dev):
@@ -315,6 +323,11 @@ def test_bad_arguments_are_refused():
 def test_nan_replace_against_its_formula(layout):
     """oard_nan_replace: status 0 leaves every bit of the output; status != 0 replaces each velocity block by noise - group mean (same
     gate as the step) and leaves the feature columns."""
+    check_nan_replace(layout)
+
+
+def check_nan_replace(layout):
+    """(shared with tests/test_object_counts.py, which runs it with one and with eight objects)"""
     dev = torch.device("cuda:0")
     rig = Rig(layout, dev)
     L = _capi.lib()
@@ -359,5 +372,7 @@ def test_nan_replace_against_its_formula(layout):
 #   ragged 1.86e-08 / 1.22e-08   wrapper 2.18e-08 / 1.92e-08   groups_1024_1_129 5.98e-09 / 5.09e-09   b64 1.41e-08 / 1.07e-08
 #   (one projection alone, as the kernel does it: offset 50 leaves 3.03e-06, 2.98e-06, 1.10e-05, 4.15e-06 - hence the second pass of
 #   DiffusionSampler._project_again)
+# one / two / four / eight objects: worst kernel err over the modes 3.32e-06 (mode 0, eight_objects), worst err / e32 2.39 (mode 4,
+# two_objects; the C entry alone: 5.92e-06, 2.39); largest group mean 2.8e-08 max|out|.
 # oard_nan_replace, object 0 (kernel err / e32): offset 0 ragged 3.97e-08 / 3.97e-08, wrapper 3.15e-08 / 3.15e-08, groups 2.37e-08 /
 # 2.37e-08; offset 50 ragged 1.97e-06 / 2.11e-06, wrapper 2.96e-06 / 2.96e-06, groups 4.12e-06 / 4.12e-06.

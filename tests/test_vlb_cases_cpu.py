@@ -36,7 +36,7 @@ def test_table_helper_reproduces_the_recorded_reference_f64(name):
     assert bool((got["contrib"] > got["nll"].abs()).all())
 
 
-@pytest.mark.parametrize("layout", list(vc.LAYOUTS) + [vc.TRAINER])
+@pytest.mark.parametrize("layout", list(vc.LAYOUTS) + [vc.TRAINER] + list(vc.OBJECT_LAYOUTS))
 def test_inputs_keep_clear_of_the_float32_discontinuities(layout):
     """In the float64 reference, for every atom of every sample of every case (in evaluation each has the t = 0 terms): the charge
     estimate that `.long()` truncates lies at least 2^-20 |value| from every non-zero integer, and every cdf difference under a log is

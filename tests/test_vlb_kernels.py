@@ -22,7 +22,7 @@ largest err / gate:
                           SNR_weight 4.38e-08 (3.78e-05) 0.04   neg_log_constants 2.83e-08 (2.83e-08) 0.06
   prepare -> terms        the same figures to the digits shown (the kernel's own z_0 / eps feed it)
 The float32 DiffusionLoss loses SNR_weight to cancellation (e32 up to 3.8e-05) and with it nll (2e-06); the kernel reads the float64-made
-table and sums in double.  All of it - four layouts, 192 cases, three tests - takes 5.5 s of test time.  Per layout: run with -s."""
+table and sums in double.  With 1, 2, 4 and 8 objects per reaction (_loss_cases.OBJECT_LAYOUTS): largest err / gate 0.23 (z_t).  All of it - four layouts, 192 cases, three tests - takes 5.5 s of test time.  Per layout: run with -s."""
 import ctypes as C
 
 import pytest
@@ -49,8 +49,9 @@ class Rig:
         self.capi, self.L = _capi, _capi.lib()
         self.batch = b = vc.Batch(layout)
         self.dev = dev
-        self.dyn = EGNNDynamics(model_config=dict(tlk.NARROW), fragment_names=["R", "TS", "P"], node_nfs=b.node_nfs, edge_nf=0,
-                                condition_nf=1, device=dev)
+        cnf, over = vc.OBJECT_MODEL.get(layout, (1, {}))
+        self.dyn = EGNNDynamics(model_config=dict(tlk.NARROW, **over), fragment_names=["R", "TS", "P"] if b.K == 3 else [f"o{k}" for k in range(b.K)],
+                                node_nfs=b.node_nfs, edge_nf=0, condition_nf=cnf, device=dev)
         self.cfg = self.dyn._config()
         with torch.cuda.device(dev):
             self.stream = torch.cuda.current_stream(dev).cuda_stream
@@ -122,7 +123,7 @@ class Rig:
         keep = [[x.clone() for x in ts] for ts in (eps_t, eps_0, z_0)]
         nll_buf, nll = self.guarded((b.B,))
         terms_buf, terms = self.guarded((5 * b.K + 2, b.B + PAD))
-        sc = (C.c_float * b.K)(*vc.SCALES[:b.K])
+        sc = (C.c_float * b.K)(*vc.lc.scales(b.K))
         with torch.cuda.device(self.dev):
             rc = self.L.oard_loss_eval_terms(C.byref(self.cfg), self.topo.handle, self.arr(eps_t), self.arr(self.net), self.arr(eps_0),
                                              self.arr(self.net0), self.arr(z_0), self.arr(self.one_hot), self.arr(self.charge), t.data_ptr(),
@@ -195,7 +196,7 @@ def check_terms(rig, case, nll, terms, bufs, worst, where):
             assert torch.equal(own[i * K + k][empty], torch.zeros(int(empty.sum()))), f"{where} object {k}: {BLOCKS[i]} of an empty group is not an exact zero"
 
 
-@pytest.mark.parametrize("layout", list(vc.LAYOUTS))
+@pytest.mark.parametrize("layout", list(vc.LAYOUTS) + list(vc.OBJECT_LAYOUTS))
 def test_prepare_matches_float64(layout):
     rig, worst = _rig(layout), tlk.Worst()
     for case in vc.cases(layout):
@@ -207,7 +208,7 @@ def test_prepare_matches_float64(layout):
     worst.report(f"eval prepare {layout}")
 
 
-@pytest.mark.parametrize("layout", list(vc.LAYOUTS))
+@pytest.mark.parametrize("layout", list(vc.LAYOUTS) + list(vc.OBJECT_LAYOUTS))
 def test_terms_match_float64(layout):
     """The kernel is fed the float32 roundings of the reference's eps_t, eps_0 and z_0."""
     rig, worst = _rig(layout), tlk.Worst()
@@ -222,7 +223,7 @@ def test_terms_match_float64(layout):
     worst.report(f"eval terms {layout}")
 
 
-@pytest.mark.parametrize("layout", list(vc.LAYOUTS))
+@pytest.mark.parametrize("layout", list(vc.LAYOUTS) + list(vc.OBJECT_LAYOUTS))
 def test_prepare_then_terms_chain(layout):
     """The kernel's own eps_t, eps_0 and z_0 into oard_loss_eval_terms: the same gates."""
     rig, worst = _rig(layout), tlk.Worst()
@@ -277,7 +278,7 @@ def test_bad_arguments_are_refused_before_a_launch():
         nll_buf, nll = rig.guarded((b.B,))
         terms_buf, terms = rig.guarded((5 * b.K + 2, b.B))
         bufs, outs = zip(*[rig.nodes() for _ in range(4)])
-        sc = (C.c_float * b.K)(*vc.SCALES[:b.K])
+        sc = (C.c_float * b.K)(*vc.lc.scales(b.K))
         f3 = rig.f3
         for cfg, topo, T, B in ((with_nf(4), rig.topo.handle, vc.T, b.B), (with_nf(21), rig.topo.handle, vc.T, b.B),
                                 (rig.cfg, multi, vc.T, b.B), (rig.cfg, rig.topo.handle, 0, b.B), (rig.cfg, rig.topo.handle, vc.T, 0)):
