@@ -622,6 +622,49 @@ int oard_matched_rmsd(const float* a_dev, int64_t lda, const float* b_dev, int64
                       float* aligned_dev /* or NULL */, int32_t* perm_dev /* or NULL */, int32_t* status_dev /* or NULL */,
                       oard_stream_t stream);
 
+/* ---- distinct structures: all-pairs RMSD per group, greedy de-duplication -------------------------------------------------------------
+ * Replaces: the two host loops over pymatgen of the reference's walkthrough - the all-pairs RMSD matrix over the transition states of
+ * one reaction (demo.py:401-480, pymatgen_rmsd(..., ignore_chirality=True) over every i < j) and the de-duplication of generated
+ * structures (demo.py:544-557: new when the smallest RMSD to the structures kept so far exceeds 0.1).  csrc/oard_pairwise.h.
+ *
+ * oard_pairwise_rmsd.  A member is a segment of ONE array: rows seg_ptr[s] .. seg_ptr[s + 1] of x_dev (row-major float32, row stride
+ * ldx >= 3 in elements, coordinates in the first three columns, read where it lies; species_dev: one int32 per row, needed with flags
+ * bit 1).  Group g is the members group_members[group_ptr[g] .. group_ptr[g + 1]] (int32 segment indices, in any order, not
+ * necessarily adjacent in x; K_g of them).  pair_ptr / mat_ptr: int64 [n_groups + 1], the exclusive prefix sums of K_g (K_g - 1) / 2 and
+ * of K_g^2; n_pairs / n_members their totals (pair_ptr[n_groups], group_ptr[n_groups]).  All tables are device arrays.
+ * out_dev: the packed row-major K_g x K_g matrices, group g at mat_ptr[g].  One wavefront per unordered pair i < j (the upper triangle
+ * row by row) runs the body of oard_kabsch_rmsd (flags bit 1 clear) or of oard_matched_rmsd (bit 1 set; exact_limit as there) with
+ * member i as a and member j as b - the same bits as those calls on explicit copies - and writes [i, j] and [j, i] from the one value;
+ * flags bit 0: the mirror image too.  A second small launch writes the diagonal: 0 for a finite, non-empty member.
+ * status_dev (or NULL), int32 packed like out_dev: 0 exact or same-order fit, 1 search, 2 species lists differ, 3 a member of more than
+ * 256 rows (bit 1 only), 4 a non-finite coordinate, 5 the two members have different row counts.  3, 4, 5, 2 are checked in this order,
+ * so a non-finite or over-long member carries one code along its whole row and column, its diagonal entry included.  Statuses 2 .. 5 give
+ * cap if cap > 0, else NaN; with a cap every value is min(value, cap).  A pair with an empty member - no rows, or a member index outside
+ * [0, n_segments) - gives NaN, status 0.
+ * Every index read from device memory is clamped before use (group boundaries to [0, n_members], segment boundaries to
+ * [0, seg_ptr[n_segments]]; a group whose matrix does not lie inside [0, mat_ptr[n_groups]) is not written): wrong tables give wrong
+ * numbers, never an access outside the arrays named.
+ * OARD_EINVAL - before any HIP call - for a null x / seg_ptr / group_members / group_ptr / pair_ptr / mat_ptr / out, a negative count,
+ * n_pairs > 0x7fffffff, ldx < 3, flags bit 1 without species_dev, exact_limit outside 0 .. 10000.  n_groups == 0: OARD_OK, no launch;
+ * n_pairs == 0: the diagonal launch alone (if n_members > 0).  No allocation, asynchronous on `stream`, capturable.
+ *
+ * oard_leader_cluster.  dist_dev / mat_ptr_dev / group_ptr_dev as above (any float32 matrices, e.g. out_dev).  One wavefront per group
+ * visits the members in the order order_dev gives (int32 group-local indices packed like the members; NULL: index order).  A member joins
+ * the leader at the smallest distance dist[member, leader] if that is <= threshold (float32 compare: a NaN is never close; a tie goes to the
+ * leader created first), else it becomes a leader.  label_dev [n_members] int32: the group-local index of each member's leader (a leader
+ * labels itself); n_clusters_dev [n_groups] int32.  A group of more than OARD_LEADER_MAX members: label -1 throughout, n_clusters -1.
+ * Integer work and float compares only.  OARD_EINVAL for a null dist / mat_ptr / group_ptr / label / n_clusters, n_groups < 0, a negative or
+ * non-finite threshold; n_groups == 0: OARD_OK, no launch. */
+#define OARD_LEADER_MAX 1024
+int oard_pairwise_rmsd(const float* x_dev, int64_t ldx, const int32_t* species_dev /* or NULL without flags bit 1 */,
+                       const int32_t* seg_ptr_dev, int64_t n_segments, const int32_t* group_members_dev, const int32_t* group_ptr_dev,
+                       const int64_t* pair_ptr_dev, const int64_t* mat_ptr_dev, int64_t n_groups, int64_t n_pairs, int64_t n_members,
+                       int flags /* bit 0: allow reflection, bit 1: match like atoms first */, float cap /* <= 0: none */,
+                       int exact_limit, float* out_dev, int32_t* status_dev /* or NULL */, oard_stream_t stream);
+int oard_leader_cluster(const float* dist_dev, const int64_t* mat_ptr_dev, const int32_t* group_ptr_dev,
+                        const int32_t* order_dev /* or NULL */, int64_t n_groups, float threshold, int32_t* label_dev,
+                        int32_t* n_clusters_dev, oard_stream_t stream);
+
 /* ---- ranking metrics: midranks per segment, AUROC, Pearson, Spearman --------------------------------------------------------------
  * Replaces: the torchmetrics objects ConfModule logs through (oa_reactdiff/trainer/pl_trainer.py:475 BinaryAUROC, :485-486
  * PearsonCorrCoef / SpearmanCorrCoef; used at :568, :579, :581), per segment instead of per call.

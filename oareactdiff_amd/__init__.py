@@ -7,7 +7,7 @@
 
 See DESIGN.md (path, kernels, measurement) and INTEGRATION.md (binding)."""
 from .dynamics import EGNNDynamics  # noqa: F401
-from .confidence import Confidence, rank_candidates, ranking_report  # noqa: F401
+from .confidence import Confidence, distinct_candidates, rank_candidates, ranking_report  # noqa: F401
 from .metrics import binary_auroc, midrank, pearson_corrcoef, rank_metrics, spearman_corrcoef  # noqa: F401
 from .sampler import DiffusionSampler  # noqa: F401
 from .loss import DiffusionLoss  # noqa: F401
@@ -16,4 +16,4 @@ from .conf_trainer import ConfidenceTrainer  # noqa: F401
 from .data import DeviceLoader, ReactionStore  # noqa: F401
 from .graph_tools import get_edges_index, get_mask_for_frag, get_n_frag_switch, get_subgraph_mask  # noqa: F401
 
-__all__ = ["EGNNDynamics", "Confidence", "rank_candidates", "ranking_report", "midrank", "rank_metrics", "binary_auroc", "pearson_corrcoef", "spearman_corrcoef", "DiffusionSampler", "DiffusionLoss", "DDPMTrainer", "ConfidenceTrainer", "ReactionStore", "DeviceLoader", "get_edges_index", "get_mask_for_frag", "get_n_frag_switch", "get_subgraph_mask"]
+__all__ = ["EGNNDynamics", "Confidence", "rank_candidates", "ranking_report", "distinct_candidates", "midrank", "rank_metrics", "binary_auroc", "pearson_corrcoef", "spearman_corrcoef", "DiffusionSampler", "DiffusionLoss", "DDPMTrainer", "ConfidenceTrainer", "ReactionStore", "DeviceLoader", "get_edges_index", "get_mask_for_frag", "get_n_frag_switch", "get_subgraph_mask"]

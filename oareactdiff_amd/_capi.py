@@ -30,7 +30,8 @@ EXPORTS = ["oard_version", "oard_supported", "oard_param_count", "oard_packed_by
            "oard_adamw_step_ema", "oard_adamw_step_dev_ema", "oard_ema_update", "oard_kabsch_rmsd", "oard_matched_rmsd", "oard_rank_metrics",
            "oard_graph_create", "oard_graph_destroy", "oard_graph_num_nodes", "oard_graph_num_edges", "oard_graph_object_rows",
            "oard_graph_is_complete", "oard_graph_workspace_bytes", "oard_graph_forward", "oard_library_stream",
-           "oard_confidence_forward", "oard_confidence_forward_train", "oard_confidence_tail_backward", "oard_dataset_gather"]
+           "oard_confidence_forward", "oard_confidence_forward_train", "oard_confidence_tail_backward", "oard_dataset_gather",
+           "oard_pairwise_rmsd", "oard_leader_cluster"]
 STAGE_RECOMPUTE, STAGE_UPDATE, STAGE_MESSAGE, STAGE_GCL_NODE, STAGE_NODE_PRE, STAGE_GCL_EDGE, STAGE_EQUI_EDGE = range(7)
 SCRATCH_XH, SCRATCH_XQ, SCRATCH_CR, SCRATCH_DCD, SCRATCH_DCR = range(1, 6)
 
@@ -101,6 +102,11 @@ def lib() -> C.CDLL:
     got = L.oard_version()
     if got != ABI_VERSION:      # e.g. an OARD_LIB override / ablation build that predates a change of oard_config: its fields would be misread
         raise OardError(f"{LIB} has ABI version {got}, this package expects {ABI_VERSION}: rebuild it "
+                        "(`python -m oareactdiff_amd.build --force`, or the script that made the OARD_LIB build)")
+    # exports added without a version step (OARD_VERSION stays 2048: no existing layout changed) are looked up by name
+    missing = [f for f in ("oard_pairwise_rmsd", "oard_leader_cluster") if not hasattr(L, f)]
+    if missing:
+        raise OardError(f"{LIB} has ABI version {got} but lacks {', '.join(missing)}: it predates them, rebuild it "
                         "(`python -m oareactdiff_amd.build --force`, or the script that made the OARD_LIB build)")
     L.oard_supported.argtypes = [cfgp]; L.oard_supported.restype = C.c_int
     L.oard_param_count.argtypes = [cfgp]; L.oard_param_count.restype = sz
@@ -182,6 +188,8 @@ def lib() -> C.CDLL:
     L.oard_kabsch_rmsd.argtypes = [vp, i64, vp, i64, vp, i64, ci, cf, vp, vp, vp, vp]; L.oard_kabsch_rmsd.restype = ci
     L.oard_matched_rmsd.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, ci, cf, ci, vp, vp, vp, vp, vp, vp]; L.oard_matched_rmsd.restype = ci
     L.oard_rank_metrics.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]; L.oard_rank_metrics.restype = ci
+    L.oard_pairwise_rmsd.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, i64, i64, ci, cf, ci, vp, vp, vp]; L.oard_pairwise_rmsd.restype = ci
+    L.oard_leader_cluster.argtypes = [vp, vp, vp, vp, i64, cf, vp, vp, vp]; L.oard_leader_cluster.restype = ci
     L.oard_dataset_gather.argtypes = [C.POINTER(OardReactionStore), vp, pvp, i64, i64, pvp, pvp, pvp, pvp, pvp, vp, vp, vp, vp, vp]
     L.oard_dataset_gather.restype = ci
     L.oard_library_stream.argtypes = [ci, pvp]; L.oard_library_stream.restype = ci

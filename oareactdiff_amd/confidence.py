@@ -89,6 +89,42 @@ def ranking_report(scores: Tensor, rmsd: Tensor, n_reactions: int, threshold: fl
     return RankingReport(spearman, top1, best, top1 < threshold, top1 - best)
 
 
+class DistinctCandidates(NamedTuple):
+    """Per reaction (`distinct_candidates`); K candidates each."""
+    label: Tensor             # [n_reactions, K] int64: the candidate index of every candidate's cluster leader (a leader labels itself)
+    is_leader: Tensor         # [n_reactions, K] bool
+    n_clusters: Tensor        # [n_reactions] int64: how many different structures the K candidates hold
+    order: Tensor             # [n_reactions, K] int64: `rank_candidates`' ordering, best score first
+
+
+def distinct_candidates(scores: Tensor, x: Tensor, sizes, n_reactions: int, threshold: float = 0.1, match_order: bool = True,
+                        ignore_chirality: bool = True, exact_limit: int = 10000) -> DistinctCandidates:
+    """How many DIFFERENT structures do the K candidates of every reaction hold, and which is the best-scored member of each?  The
+    reference's walkthrough answers with two host loops over pymatgen (the all-pairs RMSD matrix, demo.py:401-480, and the greedy
+    de-duplication at 0.1, demo.py:544-557); here it is `metrics.pairwise_rmsd` and `metrics.leader_clusters`, on the device.
+    Inputs candidate-major like `rank_candidates`: `scores` [K * n_reactions]; `x` the `[n, node_nf]` structures, segment after segment
+    (`out_samples[0][1]` of an `inpaint` over K repeats of the batch), the coordinates its first three columns and the species its last
+    column truncated to an integer, as `batch_rmsd(match_order=True)` reads it; `sizes` [K * n_reactions] their row counts.
+    The candidates of a reaction are visited in `rank_candidates`' order (descending score), so the leader of every cluster is its
+    best-scored member; a candidate joins the nearest leader within `threshold`, else it starts a cluster.  `match_order`: like atoms are
+    matched first (`matched_rmsd`), otherwise rows are compared in the order given.  A candidate with a non-finite coordinate is a
+    cluster of its own.  -> `DistinctCandidates`; `order[is_leader.gather(1, order)]` reads as "the distinct structures, best first".
+    Device tensors in, device tensors out, no host read; anything off a ROCm device raises `OardError`."""
+    from .metrics import candidate_groups, leader_clusters, pairwise_rmsd
+    _, order = rank_candidates(scores, n_reactions)
+    if not scores.is_cuda:
+        raise _capi.OardError("distinct_candidates needs scores on a ROCm device (there is no CPU fallback)")
+    K = scores.numel() // n_reactions
+    n_sizes = int(sizes.numel()) if isinstance(sizes, Tensor) else len(sizes)
+    if n_sizes != K * n_reactions:
+        raise ValueError(f"{n_sizes} sizes for {K * n_reactions} candidates")
+    dist = pairwise_rmsd(x, sizes, candidate_groups(n_reactions, K), species=x[:, -1] if match_order else None, match_order=match_order,
+                         ignore_chirality=ignore_chirality, exact_limit=exact_limit)
+    label, n_clusters = leader_clusters(dist, threshold, order=order.reshape(-1))
+    label = label.reshape(n_reactions, K)
+    return DistinctCandidates(label, label == torch.arange(K, device=label.device), n_clusters, order)
+
+
 class ConfidenceFunction(torch.autograd.Function):
     """logits = Confidence._forward(...) with the HIP training-mode forward and the reverse sweep as backward.  Inputs after the fixed
     arguments: the xh tensors, then every parameter the forward uses (`Confidence._train_params`), so that autograd routes their

@@ -2238,6 +2238,7 @@ int oard_wgrad(const float* dY, int ldY, int ncY, int o_len, int o_pad, int MO, 
 #include "oard_loss_eval.h"
 #include "oard_kabsch.h"     // k_kabsch_rmsd: the validation metric (oard_kabsch_rmsd)
 #include "oard_match.h"      // k_matched_rmsd: the same with the atoms matched first (oard_matched_rmsd)
+#include "oard_pairwise.h"   // k_pairwise_kabsch / _matched / _diag, k_leader_cluster: all-pairs RMSD per group and the de-duplication on it
 #include "oard_rank.h"       // k_rank_count, k_rank_stats: midranks per segment, AUROC / Pearson / Spearman (oard_rank_metrics)
 #include "oard_dataset.h"    // k_reaction_gather: a batch from the device-resident reaction store in one launch (oard_dataset_gather)
 extern "C" {
@@ -2586,6 +2587,47 @@ int oard_matched_rmsd(const float* a, int64_t lda, const float* b, int64_t ldb, 
     if (n_segments == 0) return OARD_OK;
     LAUNCH(F_OTHER, k_matched_rmsd, n_segments, 64, (hipStream_t)stream, a, (long long)lda, b, (long long)ldb, species_a, species_b, seg_ptr,
            flags, cap, exact_limit, rmsd, rot, aligned, perm, status);
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+// ---- all-pairs RMSD per group of structures and the greedy de-duplication on it (demo.py:401-480, 544-557; oard_pairwise.h) -------------------
+int oard_pairwise_rmsd(const float* x, int64_t ldx, const int32_t* species, const int32_t* seg_ptr, int64_t n_segments,
+                       const int32_t* group_members, const int32_t* group_ptr, const int64_t* pair_ptr, const int64_t* mat_ptr,
+                       int64_t n_groups, int64_t n_pairs, int64_t n_members, int flags, float cap, int exact_limit, float* out,
+                       int32_t* status, oard_stream_t stream) {
+    const bool matched = (flags & 2) != 0;
+    if (!x || !seg_ptr || !group_members || !group_ptr || !pair_ptr || !mat_ptr || !out || (matched && !species)) return OARD_EINVAL;
+    if (n_segments < 0 || n_segments >= 0x7fffffffLL || n_groups < 0 || n_groups >= 0x7fffffffLL || n_pairs < 0 || n_pairs > 0x7fffffffLL ||
+        n_members < 0 || n_members > 0x7fffffffLL || ldx < 3 || exact_limit < 0 || exact_limit > MATCH_LIMIT)
+        return OARD_EINVAL;
+    if (n_groups == 0) return OARD_OK;
+    const int S = (int)n_segments, G = (int)n_groups, M = (int)n_members;
+    if (n_members > 0) {
+        LAUNCH(F_OTHER, k_pairwise_diag, n_members, 64, (hipStream_t)stream, x, (long long)ldx, seg_ptr, S, group_members, group_ptr,
+               (const long long*)mat_ptr, G, M, matched ? 1 : 0, cap, out, status);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_pairs == 0) return OARD_OK;
+    if (matched)
+        LAUNCH(F_OTHER, k_pairwise_matched, n_pairs, 64, (hipStream_t)stream, x, (long long)ldx, species, seg_ptr, S, group_members, group_ptr,
+               (const long long*)pair_ptr, (const long long*)mat_ptr, G, M, flags & 1, cap, exact_limit, out, status);
+    else
+        LAUNCH(F_OTHER, k_pairwise_kabsch, n_pairs, 64, (hipStream_t)stream, x, (long long)ldx, seg_ptr, S, group_members, group_ptr,
+               (const long long*)pair_ptr, (const long long*)mat_ptr, G, M, flags & 1, cap, out, status);
+    HIP_TRY(hipGetLastError());
+    return OARD_OK;
+}
+
+static_assert(LEADER_MAX == OARD_LEADER_MAX, "include/oard.h states the limit of k_leader_cluster");
+int oard_leader_cluster(const float* dist, const int64_t* mat_ptr, const int32_t* group_ptr, const int32_t* order, int64_t n_groups,
+                        float threshold, int32_t* label, int32_t* n_clusters, oard_stream_t stream) {
+    if (!dist || !mat_ptr || !group_ptr || !label || !n_clusters || n_groups < 0 || n_groups >= 0x7fffffffLL || !(threshold >= 0.f) ||
+        !std::isfinite(threshold))
+        return OARD_EINVAL;
+    if (n_groups == 0) return OARD_OK;
+    LAUNCH(F_OTHER, k_leader_cluster, n_groups, 64, (hipStream_t)stream, dist, (const long long*)mat_ptr, group_ptr, order, (int)n_groups,
+           threshold, label, n_clusters);
     HIP_TRY(hipGetLastError());
     return OARD_OK;
 }

@@ -22,6 +22,7 @@
 //      so no further pass forms it); the smaller RMSD is kept, with the improper map R' diag(1, 1, -1) (a tie keeps the rotation).
 // Special segments: empty -> NaN; any non-finite coordinate -> cap if cap > 0 else NaN (the reference's `except: rmsd = 1.0`); with
 // a cap the result is min(rmsd, cap) (its `min(rmsd, 1.0)`).  Their rot / aligned entries are NaN.
+// The kernel is one call of kabsch_body, which k_pairwise_kabsch (csrc/oard_pairwise.h) calls too, with two members of one array.
 #pragma once
 #include "oard_kernels.h"
 
@@ -92,21 +93,26 @@ OARD_DEV double kabsch_rotation(const double (&S)[3][3], double (&R)[3][3]) {
     return lam;
 }
 
-OARD_KERNEL __global__ __launch_bounds__(64) void k_kabsch_rmsd(const float* __restrict__ a, long long lda, const float* __restrict__ b,
-                                                                long long ldb, const int* __restrict__ seg_ptr, int flags, float cap,
-                                                                float* __restrict__ rmsd, float* __restrict__ rot,
-                                                                float* __restrict__ aligned) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const long long r0 = seg_ptr[g];
-    const int n = (int)((long long)seg_ptr[g + 1] - r0);
+// One value into its output slot(s): a caller with two (the [i, j] and [j, i] entries of a pair matrix, csrc/oard_pairwise.h) gets the same
+// bits in both; p2 / s / s2 may be null.
+OARD_DEV void kabsch_store(float* p, float* p2, float v, int* s, int* s2, int code) {
+    *p = v;
+    if (p2 != nullptr) *p2 = v;
+    if (s != nullptr) *s = code;
+    if (s2 != nullptr) *s2 = code;
+}
+
+// The body of k_kabsch_rmsd for ONE segment, shared with k_pairwise_kabsch (csrc/oard_pairwise.h): A / B are the first rows of the target
+// and of the structure fitted onto it, n the rows of both.  rmsd (and rmsd2, status, status2 if not null) are the slots of this segment;
+// rot its nine floats, aligned its n rows (or null).  The status written is 0, or 4 for a non-finite coordinate (oard_match.h's code).
+OARD_DEV void kabsch_body(const float* A, long long lda, const float* B, long long ldb, int n, int lane, int flags, float cap, float* rmsd,
+                          float* rmsd2, int* status, int* status2, float* rot, float* aligned) {
     const float fnan = __builtin_nanf("");
     if (n <= 0) {
-        if (lane == 0) rmsd[g] = fnan;
-        if (rot != nullptr && lane < 9) rot[(size_t)g * 9 + lane] = fnan;
+        if (lane == 0) kabsch_store(rmsd, rmsd2, fnan, status, status2, 0);
+        if (rot != nullptr && lane < 9) rot[lane] = fnan;
         return;
     }
-    const float* A = a + (size_t)r0 * (size_t)lda;
-    const float* B = b + (size_t)r0 * (size_t)ldb;
     // ---- pass 1: centroids, and is every coordinate finite ----------------------------------------
     double ca0 = 0, ca1 = 0, ca2 = 0, cb0 = 0, cb1 = 0, cb2 = 0;
     bool bad = false;
@@ -119,11 +125,11 @@ OARD_KERNEL __global__ __launch_bounds__(64) void k_kabsch_rmsd(const float* __r
         cb0 += (double)b0; cb1 += (double)b1; cb2 += (double)b2;
     }
     if (__any(bad ? 1 : 0)) {
-        if (lane == 0) rmsd[g] = cap > 0.f ? cap : fnan;
-        if (rot != nullptr && lane < 9) rot[(size_t)g * 9 + lane] = fnan;
+        if (lane == 0) kabsch_store(rmsd, rmsd2, cap > 0.f ? cap : fnan, status, status2, 4);
+        if (rot != nullptr && lane < 9) rot[lane] = fnan;
         if (aligned != nullptr)
             for (int k = lane; k < n; k += 64) {
-                float* o = aligned + ((size_t)r0 + (size_t)k) * 3;
+                float* o = aligned + (size_t)k * 3;
                 o[0] = fnan; o[1] = fnan; o[2] = fnan;
             }
         return;
@@ -185,9 +191,9 @@ OARD_KERNEL __global__ __launch_bounds__(64) void k_kabsch_rmsd(const float* __r
     if (lane == 0) {
         float r = (float)best;
         if (cap > 0.f) r = fminf(r, cap);
-        rmsd[g] = r;
+        kabsch_store(rmsd, rmsd2, r, status, status2, 0);
         if (rot != nullptr) {
-            float* o = rot + (size_t)g * 9;
+            float* o = rot;
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -198,9 +204,21 @@ OARD_KERNEL __global__ __launch_bounds__(64) void k_kabsch_rmsd(const float* __r
         for (int k = lane; k < n; k += 64) {
             const float* pb = B + (size_t)k * (size_t)ldb;
             const double y0 = (double)pb[0] - cb0, y1 = (double)pb[1] - cb1, y2 = (double)pb[2] - cb2;
-            float* o = aligned + ((size_t)r0 + (size_t)k) * 3;
+            float* o = aligned + (size_t)k * 3;
             o[0] = (float)(M[0][0] * y0 + M[0][1] * y1 + M[0][2] * y2 + ca0);
             o[1] = (float)(M[1][0] * y0 + M[1][1] * y1 + M[1][2] * y2 + ca1);
             o[2] = (float)(M[2][0] * y0 + M[2][1] * y1 + M[2][2] * y2 + ca2);
         }
+}
+
+OARD_KERNEL __global__ __launch_bounds__(64) void k_kabsch_rmsd(const float* __restrict__ a, long long lda, const float* __restrict__ b,
+                                                                long long ldb, const int* __restrict__ seg_ptr, int flags, float cap,
+                                                                float* __restrict__ rmsd, float* __restrict__ rot,
+                                                                float* __restrict__ aligned) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const long long r0 = seg_ptr[g];
+    const int n = (int)((long long)seg_ptr[g + 1] - r0);
+    const size_t row = n > 0 ? (size_t)r0 : 0;              // an empty segment reads nothing: no address is formed from its r0
+    kabsch_body(a + row * (size_t)lda, lda, b + row * (size_t)ldb, ldb, n, lane, flags, cap, rmsd + g, nullptr, nullptr, nullptr,
+                rot != nullptr ? rot + (size_t)g * 9 : nullptr, aligned != nullptr ? aligned + row * 3 : nullptr);
 }

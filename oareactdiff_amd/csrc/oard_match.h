@@ -25,6 +25,7 @@
 // Special segments (rot / aligned NaN, perm the identity): more than MATCH_MAX rows -> status 3; a non-finite coordinate -> status 4;
 // species lists that differ as multisets -> status 2 (checked in this order); each gives cap if cap > 0 else NaN (the reference's
 // `except: rmsd = 1.0`).  An empty segment gives NaN, status 0.
+// The kernel is one call of matched_body, which k_pairwise_matched (csrc/oard_pairwise.h) calls too, with two members of one array.
 #pragma once
 #include "oard_kabsch.h"
 
@@ -184,33 +185,26 @@ OARD_DEV void match_assign_block(MatchLds& L, int o, int m, int lane) {
     __syncthreads();
 }
 
-OARD_KERNEL __global__ __launch_bounds__(64) void k_matched_rmsd(const float* __restrict__ a, long long lda, const float* __restrict__ b,
-                                                                 long long ldb, const int* __restrict__ species_a,
-                                                                 const int* __restrict__ species_b, const int* __restrict__ seg_ptr,
-                                                                 int flags, float cap, int exact_limit, float* __restrict__ rmsd,
-                                                                 float* __restrict__ rot, float* __restrict__ aligned,
-                                                                 int* __restrict__ perm, int* __restrict__ status) {
-    __shared__ MatchLds L;
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const long long r0 = seg_ptr[g];
-    const long long nl = (long long)seg_ptr[g + 1] - r0;
+// The body of k_matched_rmsd for ONE segment, shared with k_pairwise_matched (csrc/oard_pairwise.h): A / B and SA / SB are the first rows
+// and species of the target and of the structure fitted onto it, nl the rows of both, L the workgroup's LDS.  rmsd (and rmsd2, status,
+// status2 if not null) are the slots of this segment, rot its nine floats, aligned / perm its nl rows (or null); perm holds row0 + the
+// row inside the segment.
+OARD_DEV void matched_body(MatchLds& L, const float* A, long long lda, const float* B, long long ldb, const int* SA, const int* SB,
+                           long long nl, long long row0, int lane, int flags, float cap, int exact_limit, float* rmsd, float* rmsd2,
+                           int* status, int* status2, float* rot, float* aligned, int* perm) {
     const float fnan = __builtin_nanf("");
     if (nl <= 0) {
-        if (lane == 0) { rmsd[g] = fnan; if (status != nullptr) status[g] = 0; }
-        if (rot != nullptr && lane < 9) rot[(size_t)g * 9 + lane] = fnan;
+        if (lane == 0) kabsch_store(rmsd, rmsd2, fnan, status, status2, 0);
+        if (rot != nullptr && lane < 9) rot[lane] = fnan;
         return;
     }
-    const float* A = a + (size_t)r0 * (size_t)lda;
-    const float* B = b + (size_t)r0 * (size_t)ldb;
-    const int* SA = species_a + r0;
-    const int* SB = (species_b != nullptr ? species_b : species_a) + r0;
     // a special segment: the status, cap or NaN, NaN maps, the identity permutation (nl rows: also more than MATCH_MAX of them)
     auto special = [&](int code) {
-        if (lane == 0) { rmsd[g] = cap > 0.f ? cap : fnan; if (status != nullptr) status[g] = code; }
-        if (rot != nullptr && lane < 9) rot[(size_t)g * 9 + lane] = fnan;
+        if (lane == 0) kabsch_store(rmsd, rmsd2, cap > 0.f ? cap : fnan, status, status2, code);
+        if (rot != nullptr && lane < 9) rot[lane] = fnan;
         for (long long k = lane; k < nl; k += 64) {
-            if (aligned != nullptr) { float* o = aligned + ((size_t)r0 + (size_t)k) * 3; o[0] = fnan; o[1] = fnan; o[2] = fnan; }
-            if (perm != nullptr) perm[r0 + k] = (int)(r0 + k);
+            if (aligned != nullptr) { float* o = aligned + (size_t)k * 3; o[0] = fnan; o[1] = fnan; o[2] = fnan; }
+            if (perm != nullptr) perm[k] = (int)(row0 + k);
         }
     };
     if (nl > MATCH_MAX) { special(3); return; }
@@ -443,10 +437,9 @@ OARD_KERNEL __global__ __launch_bounds__(64) void k_matched_rmsd(const float* __
     if (lane == 0) {
         float r = (float)best;
         if (cap > 0.f) r = fminf(r, cap);
-        rmsd[g] = r;
-        if (status != nullptr) status[g] = exact ? 0 : 1;
+        kabsch_store(rmsd, rmsd2, r, status, status2, exact ? 0 : 1);
         if (rot != nullptr) {
-            float* o = rot + (size_t)g * 9;
+            float* o = rot;
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -455,8 +448,8 @@ OARD_KERNEL __global__ __launch_bounds__(64) void k_matched_rmsd(const float* __
     }
     for (int t = lane; t < n; t += 64) {
         const int c = L.qbest[t];
-        const size_t row = (size_t)r0 + (size_t)L.ord_a[t];
-        if (perm != nullptr) perm[row] = (int)(r0 + L.ord_b[c]);
+        const size_t row = (size_t)L.ord_a[t];
+        if (perm != nullptr) perm[row] = (int)(row0 + L.ord_b[c]);
         if (aligned != nullptr) {
             const double y0 = L.y[0][c], y1 = L.y[1][c], y2 = L.y[2][c];
             float* o = aligned + row * 3;
@@ -465,4 +458,21 @@ OARD_KERNEL __global__ __launch_bounds__(64) void k_matched_rmsd(const float* __
             o[2] = (float)(M[2][0] * y0 + M[2][1] * y1 + M[2][2] * y2 + ca2);
         }
     }
+}
+
+OARD_KERNEL __global__ __launch_bounds__(64) void k_matched_rmsd(const float* __restrict__ a, long long lda, const float* __restrict__ b,
+                                                                 long long ldb, const int* __restrict__ species_a,
+                                                                 const int* __restrict__ species_b, const int* __restrict__ seg_ptr,
+                                                                 int flags, float cap, int exact_limit, float* __restrict__ rmsd,
+                                                                 float* __restrict__ rot, float* __restrict__ aligned,
+                                                                 int* __restrict__ perm, int* __restrict__ status) {
+    __shared__ MatchLds L;
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const long long r0 = seg_ptr[g];
+    const long long nl = (long long)seg_ptr[g + 1] - r0;
+    const size_t row = nl > 0 ? (size_t)r0 : 0;             // an empty segment reads nothing: no address is formed from its r0
+    matched_body(L, a + row * (size_t)lda, lda, b + row * (size_t)ldb, ldb, species_a + row,
+                 (species_b != nullptr ? species_b : species_a) + row, nl, r0, lane, flags, cap, exact_limit, rmsd + g, nullptr,
+                 status != nullptr ? status + g : nullptr, nullptr, rot != nullptr ? rot + (size_t)g * 9 : nullptr,
+                 aligned != nullptr ? aligned + row * 3 : nullptr, perm != nullptr ? perm + row : nullptr);
 }

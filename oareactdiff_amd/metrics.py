@@ -23,6 +23,12 @@ RANKING METRICS (`oard_rank_metrics`, csrc/oard_rank.h): `rank_metrics(score, ta
 sort, float64 sums in a fixed order: ties are exact, ragged segments are one launch, a segment's bits depend on its own values alone, and
 nothing is read back.  `binary_auroc`, `pearson_corrcoef` and `spearman_corrcoef` select one column.
 
+DISTINCT STRUCTURES (`oard_pairwise_rmsd`, `oard_leader_cluster`, csrc/oard_pairwise.h): `pairwise_rmsd(x, sizes, groups)` is the all-pairs
+RMSD matrix of every group of structures of ONE coordinate array - the reference's host loop over pymatgen (demo.py:401-480) -, one
+wavefront per pair running the body of `kabsch_rmsd` / `matched_rmsd` (the same bits, nothing gathered); `leader_clusters` the reference's
+greedy de-duplication on such matrices (demo.py:544-557), one wavefront per group, exact.  `confidence.distinct_candidates` combines them
+with `rank_candidates`.
+
 No CPU fallback: tensors that are not on a ROCm device raise `OardError`, as everywhere else in the package."""
 from __future__ import annotations
 
@@ -273,3 +279,168 @@ def pearson_corrcoef(pred: Tensor, target: Tensor, sizes: Union[Tensor, Sequence
 def spearman_corrcoef(pred: Tensor, target: Tensor, sizes: Union[Tensor, Sequence[int], None] = None) -> Tensor:
     """`rank_metrics(...).spearman`: torchmetrics' `SpearmanCorrCoef` (pl_trainer.py:486) per segment."""
     return rank_metrics(pred, target, sizes).spearman
+
+
+# ---- distinct structures: all-pairs RMSD per group and the greedy de-duplication (csrc/oard_pairwise.h) ---------------------------------
+PAIR_UNEQUAL = 5              # status of a pair whose members have different row counts (0 .. 4: the MATCH_* codes above)
+LEADER_MAX = 1024             # members per group of leader_clusters (OARD_LEADER_MAX of include/oard.h)
+
+
+def candidate_groups(n_reactions: int, K: int) -> List[List[int]]:
+    """The groups of the candidate-major layout (`confidence.rank_candidates`): K repeats of a batch of `n_reactions` reactions, segment
+    `k * n_reactions + r` being candidate k of reaction r -> group r = [r, n_reactions + r, 2 n_reactions + r, ...]."""
+    if n_reactions < 0 or K < 0:
+        raise ValueError("n_reactions and K must be non-negative")
+    return [[k * n_reactions + r for k in range(K)] for r in range(n_reactions)]
+
+
+class PairwiseRmsd:
+    """What `pairwise_rmsd` returns: `flat`, ONE float32 device allocation holding the `[K_g, K_g]` matrices of all groups one behind the
+    other; `group_ptr` / `mat_ptr`, host tuples (group g has `group_ptr[g + 1] - group_ptr[g]` members, its matrix starts at
+    `mat_ptr[g]`); `status`, packed like `flat` (int32), if it was asked for."""
+
+    def __init__(self, flat: Tensor, group_ptr, mat_ptr, status: Optional[Tensor], tables) -> None:
+        self.flat, self.group_ptr, self.mat_ptr, self.status = flat, tuple(group_ptr), tuple(mat_ptr), status
+        self._tables = tables                          # (int32 device: members + group_ptr, int64 device: pair_ptr + mat_ptr)
+
+    @property
+    def n_groups(self) -> int:
+        return len(self.group_ptr) - 1
+
+    def size(self, g: int) -> int:
+        return self.group_ptr[g + 1] - self.group_ptr[g]
+
+    def _view(self, t: Tensor, g: int) -> Tensor:
+        K = self.size(g)
+        return t[self.mat_ptr[g]: self.mat_ptr[g] + K * K].view(K, K)
+
+    def matrix(self, g: int) -> Tensor:
+        """The `[K_g, K_g]` matrix of group g: a view of `flat`."""
+        return self._view(self.flat, g)
+
+    def status_matrix(self, g: int) -> Tensor:
+        if self.status is None:
+            raise ValueError("the status was not asked for (return_status=True)")
+        return self._view(self.status, g)
+
+    def stacked(self) -> Tensor:
+        """`[G, K, K]`, a view of `flat`, when every group has K members; ValueError otherwise."""
+        sizes = {self.size(g) for g in range(self.n_groups)}
+        if len(sizes) > 1:
+            raise ValueError(f"the groups have different sizes ({sorted(sizes)}): use matrix(g)")
+        K = sizes.pop() if sizes else 0
+        return self.flat.view(self.n_groups, K, K)
+
+
+def _group_tables(groups, S: int, dev):
+    """Host `groups` -> (host group_ptr, pair_ptr, mat_ptr; device int32 [members | group_ptr], device int64 [pair_ptr | mat_ptr])."""
+    if isinstance(groups, Tensor):
+        if groups.is_cuda:
+            raise ValueError("groups fixes the shape of the result and must be host data (a sequence of sequences of segment indices), "
+                             "not a device tensor")
+        groups = groups.tolist()
+    groups = [[int(m) for m in grp] for grp in groups]
+    members, group_ptr, pair_ptr, mat_ptr = [], [0], [0], [0]
+    for grp in groups:
+        if any(m < 0 or m >= S for m in grp):
+            raise ValueError(f"a group names a segment outside 0 .. {S - 1}")
+        K = len(grp)
+        members += grp
+        group_ptr.append(group_ptr[-1] + K)
+        pair_ptr.append(pair_ptr[-1] + K * (K - 1) // 2)
+        mat_ptr.append(mat_ptr[-1] + K * K)
+    if pair_ptr[-1] > 0x7fffffff or group_ptr[-1] > 0x7fffffff:
+        raise ValueError(f"{pair_ptr[-1]} pairs: at most 2^31 - 1 per call")
+    t32 = torch.tensor(members + group_ptr, dtype=torch.int32, device=dev)
+    t64 = torch.tensor(pair_ptr + mat_ptr, dtype=torch.int64, device=dev)
+    return group_ptr, pair_ptr, mat_ptr, t32, t64
+
+
+def pairwise_rmsd(x: Tensor, sizes: Union[Tensor, Sequence[int]], groups, species=None, match_order: bool = False,
+                  ignore_chirality: bool = True, cap: Optional[float] = None, exact_limit: int = 10000,
+                  return_status: bool = False) -> PairwiseRmsd:
+    """All-pairs RMSD inside every group of structures (`oard_pairwise_rmsd`; the reference's matrix over the transition states of a
+    reaction, demo.py:401-480).  Segment s is the next `sizes[s]` rows of `x` (coordinates in the first three columns, read where they
+    lie; `sizes` as for `kabsch_rmsd`, a device tensor is never read back).  `groups`: a HOST sequence of sequences of segment indices -
+    it fixes the shape of the result -; the members of a group need not be adjacent (`candidate_groups` gives the candidate-major ones).
+    Entry [i, j] of a group's matrix is `kabsch_rmsd` (or with `match_order` `matched_rmsd`, `species` one integer per row of `x`) of
+    member i as the target and member j fitted onto it, bit for bit; [j, i] is the same value, the diagonal is 0.  One wavefront per pair,
+    no gathered copy of the coordinates.  -> `PairwiseRmsd`.
+    `return_status`: per entry 0 exact / same-order, 1 search, 2 species lists differ, 3 more than 256 rows (`match_order` only),
+    4 a non-finite coordinate, 5 different row counts; 2 .. 5 give `cap` (None: NaN), and a non-finite or over-long member does so along
+    its whole row and column, the diagonal included.  An empty member gives NaN."""
+    x = _coords(x, "x")
+    dev = x.device
+    n = int(x.shape[0])
+    if cap is not None and not float(cap) > 0.0:
+        raise ValueError("cap must be positive (None: no cap)")
+    if not 0 <= int(exact_limit) <= 10000:
+        raise ValueError("exact_limit must lie in 0 .. 10000")
+    if match_order and species is None:
+        raise ValueError("match_order needs species (one integer per row of x)")
+    sp = _species(species, "species", n, dev) if match_order else None
+    seg_ptr, S = _segments(sizes, n, dev, limit=MATCH_MAX_ROWS if match_order else None)
+    group_ptr, pair_ptr, mat_ptr, t32, t64 = _group_tables(groups, S, dev)
+    G, M = len(group_ptr) - 1, group_ptr[-1]
+    flat = torch.empty(mat_ptr[-1], dtype=torch.float32, device=dev)
+    status = torch.zeros(mat_ptr[-1], dtype=torch.int32, device=dev) if return_status else None
+    if G and M:
+        if n == 0:                                   # an empty tensor has no address; every member is empty and nothing is read
+            x = torch.zeros(1, 3, dtype=torch.float32, device=dev)
+            sp = None if sp is None else torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _capi.lib().oard_pairwise_rmsd(x.data_ptr(), x.stride(0) if x.shape[0] > 1 else max(int(x.shape[1]), 3),
+                                                None if sp is None else sp.data_ptr(), seg_ptr.data_ptr(), S, t32.data_ptr(),
+                                                t32[M:].data_ptr(), t64.data_ptr(), t64[G + 1:].data_ptr(), G, pair_ptr[-1], M,
+                                                (1 if ignore_chirality else 0) | (2 if match_order else 0),
+                                                0.0 if cap is None else float(cap), int(exact_limit), flat.data_ptr(),
+                                                None if status is None else status.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream)
+        _capi.check(rc, "oard_pairwise_rmsd")
+    return PairwiseRmsd(flat, group_ptr, mat_ptr, status, (t32, t64))
+
+
+def leader_clusters(dist, threshold: float = 0.1, order: Optional[Tensor] = None):
+    """The reference's greedy de-duplication (demo.py:544-557) per group, on the device (`oard_leader_cluster`): the members are visited
+    in index order, or in the order `order` gives (a device int tensor of group-local indices, packed by group like the members); a member
+    joins the leader at the smallest distance if that distance is `<= threshold` (a tie: the leader created first; a NaN is never close),
+    else it becomes a leader.  `dist`: a `PairwiseRmsd`, or a float32 device tensor `[G, K, K]` (`[K, K]`: one group).
+    -> (label, n_clusters): `label` int64 `[sum K_g]` packed by group, the group-local index of every member's leader (a leader labels
+    itself); `n_clusters` int64 `[G]`.  A group of more than 1024 members gets -1 throughout.  Device tensors, no host read."""
+    if not (float(threshold) >= 0.0) or float(threshold) == float("inf"):
+        raise ValueError("threshold must be finite and non-negative")
+    if isinstance(dist, PairwiseRmsd):
+        flat, group_ptr = dist.flat, dist.group_ptr
+        t32, t64 = dist._tables
+        G, M = dist.n_groups, group_ptr[-1]
+        gp, mp = t32[M:], t64[G + 1:]
+        if not flat.is_cuda:
+            raise _capi.OardError("leader_clusters needs dist on a ROCm device (there is no CPU fallback)")
+    else:
+        if not isinstance(dist, Tensor) or dist.dim() not in (2, 3) or dist.shape[-1] != dist.shape[-2]:
+            raise ValueError("dist must be a PairwiseRmsd or a [G, K, K] / [K, K] tensor")
+        if not dist.is_cuda:
+            raise _capi.OardError("leader_clusters needs dist on a ROCm device (there is no CPU fallback)")
+        flat = dist.to(torch.float32).contiguous().reshape(-1)
+        G, K = (1 if dist.dim() == 2 else int(dist.shape[0])), int(dist.shape[-1])
+        M = G * K
+        gp = torch.arange(0, M + 1, max(K, 1), dtype=torch.int32, device=flat.device) if K else torch.zeros(G + 1, dtype=torch.int32, device=flat.device)
+        mp = torch.arange(0, G + 1, dtype=torch.int64, device=flat.device) * (K * K)
+    dev = flat.device
+    if order is not None:
+        if not isinstance(order, Tensor) or not order.is_cuda or order.device != dev:
+            raise ValueError("order must be a device int tensor on dist's device")
+        if order.is_floating_point() or int(order.numel()) != M:
+            raise ValueError(f"order must hold one integer per member ({M}), packed by group")
+        order = order.reshape(-1).to(torch.int32).contiguous()
+    label = torch.full((M,), -1, dtype=torch.int32, device=dev)
+    n_clusters = torch.zeros(G, dtype=torch.int32, device=dev)
+    if G:
+        probe = flat if flat.numel() else torch.zeros(1, dtype=torch.float32, device=dev)
+        lab = label if M else torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _capi.lib().oard_leader_cluster(probe.data_ptr(), mp.data_ptr(), gp.data_ptr(),
+                                                 None if order is None or not M else order.data_ptr(), G, float(threshold),
+                                                 lab.data_ptr(), n_clusters.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _capi.check(rc, "oard_leader_cluster")
+    return label.long(), n_clusters.long()
